@@ -16,6 +16,14 @@ the single-GPU engine; N > 1 splits the 32 layers into N contiguous stages (one 
     python bench.py                               # N=1 defaults
     python bench.py --gpus 8                      # spawns its 8 ranks (launch.py)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+    python bench.py --dump-outputs DIR            # + DIR/output_ids.npy of the last timed step
+
+A plain run does only what the headline figure needs: set-up, --warmup waves, --steps timed
+waves, the result line (``ms_per_step`` = seconds of one timed wave x 1000). Prompts and
+sampling seeds depend on the arguments alone, so ``--dump-outputs`` of two builds can be
+compared output for output. At N = 1 the plain run tunes and captures only the decode bucket
+its waves use; ``--full`` adds what the figure does not need (today: every decode bucket up
+to --batch, the serving engine's start-up).
 
 Without torchrun's environment, ``--gpus N > 1`` starts N child ranks itself (one per GPU,
 127.0.0.1 rendezvous) before anything touches the GPU, waits for them and exits with the
@@ -89,6 +97,26 @@ def make_prompts(n, prompt_len, vocab, seed):
     return rng.integers(lo, hi, size=(n, prompt_len)).tolist()
 
 
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: what the last timed wave returned to its caller, one row of sampled
+    token ids per request in request order (``output_ids.npy``, float32: ids are far below
+    2^24; rows shorter than the longest are padded with -1). Above 64 MB a fixed, seeded
+    sample of the rows is kept, in request order."""
+    width = max(len(o.output_ids) for o in outs)
+    ids = np.full((len(outs), width), -1.0, dtype=np.float32)
+    for i, o in enumerate(outs):
+        ids[i, :len(o.output_ids)] = o.output_ids
+    keep = MAX_DUMP_BYTES // (4 * width)
+    if len(outs) > keep:
+        ids = ids[np.sort(np.random.default_rng(0).choice(len(outs), keep, replace=False))]
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "output_ids.npy", ids)
+
+
 def run_single(args, barrier=None):
     from distributed_llm_inferencing_amd.engine import SamplingParams
     from distributed_llm_inferencing_amd.engine.llm_engine import LLMEngine
@@ -100,11 +128,18 @@ def run_single(args, barrier=None):
                     max_prefill_tokens=max(args.batch * args.prompt_len, 8192))
     sp = SamplingParams(max_length=args.max_length, temperature=0.8, top_k=50, top_p=0.95,
                         ignore_eos=True)
-    eng.warmup()
+    # every request of a wave has the same lengths, so all decode steps run --batch rows: a
+    # plain run tunes and captures that one decode bucket (a bucket met all the same is tuned
+    # and captured on first use). Tuning all 18 buckets up to 512, as a serving engine does at
+    # start-up, took 32 s of a 44 s run; --full still does it.
+    eng.warmup(buckets=None if args.full else [args.batch])
+
+    last = []                 # the last wave's RequestOutputs (--dump-outputs)
 
     def wave(seed):
         prompts = make_prompts(args.batch, args.prompt_len, eng.cfg.vocab_size, seed)
         outs = eng.generate(prompts, sp)
+        last[:] = outs
         return sum(len(o.output_ids) for o in outs), [o.latency_s for o in outs]
 
     for w in range(args.warmup):
@@ -125,7 +160,8 @@ def run_single(args, barrier=None):
         barrier()
     dt = time.perf_counter() - t0
     return {"tokens": toks, "seconds": dt, "latencies": lats, "global_batch": args.batch,
-            "parallelism": "single", "engine": eng.stats.snapshot(), "data_plane": "none"}
+            "parallelism": "single", "engine": eng.stats.snapshot(), "data_plane": "none",
+            "last_outputs": last}
 
 
 def run_data_parallel(args, world, rank):
@@ -155,7 +191,8 @@ def run_data_parallel(args, world, rank):
         return None
     return {"tokens": float(t[1].item()), "seconds": float(mx[0].item()),
             "latencies": [x for l in lats for x in l], "global_batch": args.batch * world,
-            "parallelism": f"dp{world}", "data_plane": "none", "ranks_info": infos}
+            "parallelism": f"dp{world}", "data_plane": "none", "ranks_info": infos,
+            "last_outputs": res["last_outputs"]}
 
 
 def run_pipeline(args, world, rank):
@@ -198,7 +235,16 @@ def main():
                     help="N>1: pp = layer-sharded pipeline (dense, default), ep = expert "
                          "parallel (MoE), tp = tensor-parallel ablation, dp = independent "
                          "replicas")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the token ids that the last timed "
+                         "step returned (rank 0's requests) to DIR/output_ids.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also do what the headline figure does not need: N=1 tunes and "
+                         "captures every decode batch bucket at start-up, as a serving "
+                         "engine does, instead of the one bucket the waves use")
     a = ap.parse_args()
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     from distributed_llm_inferencing_amd import launch
     if a.gpus > 1 and not launch.under_launcher():
@@ -220,6 +266,8 @@ def main():
         res = run_single(a)
     if rank != 0 or res is None:
         return
+    if a.dump_outputs:
+        dump_outputs(res["last_outputs"], a.dump_outputs)
     tok_s = res["tokens"] / res["seconds"]
     p50 = statistics.median(res["latencies"]) if res["latencies"] else None
     base = _baseline_value()

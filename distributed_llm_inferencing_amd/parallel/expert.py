@@ -608,10 +608,12 @@ def bench_expert_parallel(args, world, rank, make_prompts):
     from ..engine.sequence import SamplingParams
     sp = SamplingParams(max_length=args.max_length, temperature=0.8, top_k=50, top_p=0.95,
                         ignore_eos=True)
+    last = []                 # the last wave's RequestOutputs (bench --dump-outputs)
 
     def wave(seed):
         outs = eng.generate(make_prompts(args.batch, args.prompt_len, eng.cfg.vocab_size,
                                          seed * 100 + rank), sp)
+        last[:] = outs
         return sum(len(o.output_ids) for o in outs), [o.latency_s for o in outs]
 
     for w in range(args.warmup):
@@ -647,7 +649,7 @@ def bench_expert_parallel(args, world, rank, make_prompts):
     return {"tokens": int(tt.item()), "seconds": float(dt.item()),
             "latencies": torch.cat(gathered).tolist(), "global_batch": args.batch * world,
             "parallelism": f"dp{world}-ep{world}", "data_plane": eng.data_plane,
-            "ranks_info": infos,
+            "ranks_info": infos, "last_outputs": last,
             "engine": {"control_plane": eng.control_plane,
                        "lockstep_ms_per_step": round(1e3 * eng.lockstep_s
                                                      / max(1, eng.lockstep_syncs), 4),

@@ -1010,11 +1010,13 @@ def bench_pipeline(args, world: int, rank: int, make_prompts):
                         ignore_eos=True)
     per_wave = args.batch * eng.microbatches       # M microbatches of --batch requests
     bufs = None if rank == 0 else _StageBuffers(eng.stage, eng.channel)
+    last = []                 # the last wave's RequestOutputs (bench --dump-outputs)
 
     def wave(seed):
         if rank == 0:
             outs = eng.generate(make_prompts(per_wave, args.prompt_len, eng.cfg.vocab_size, seed),
                                 sp)
+            last[:] = outs
             return sum(len(o.output_ids) for o in outs), [o.latency_s for o in outs]
         serve_session(eng.stage, eng.channel, bufs)
         return 0, []
@@ -1067,7 +1069,7 @@ def bench_pipeline(args, world: int, rank: int, make_prompts):
     snap["control_plane"] = eng.channel.ctrl_kind
     return {"tokens": toks, "seconds": float(dt.item()), "latencies": lats,
             "global_batch": per_wave, "parallelism": f"pp{world}", "engine": snap,
-            "data_plane": eng.channel.data_plane, "ranks_info": infos}
+            "data_plane": eng.channel.data_plane, "ranks_info": infos, "last_outputs": last}
 
 
 def run_one_session(eng: DistributedPipelineEngine):

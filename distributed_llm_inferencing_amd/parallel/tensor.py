@@ -120,10 +120,12 @@ def bench_tensor_parallel(args, world, rank, make_prompts):
     from ..engine.sequence import SamplingParams
     sp = SamplingParams(max_length=args.max_length, temperature=0.8, top_k=50, top_p=0.95,
                         ignore_eos=True, seed=1234)
+    last = []                 # the last wave's RequestOutputs (bench --dump-outputs)
 
     def wave(seed):
         outs = eng.generate(make_prompts(batch, args.prompt_len, eng.full_cfg.vocab_size,
                                          seed), sp)
+        last[:] = outs
         return sum(len(o.output_ids) for o in outs), [o.latency_s for o in outs]
 
     for w in range(args.warmup):
@@ -153,4 +155,4 @@ def bench_tensor_parallel(args, world, rank, make_prompts):
     # every rank produced the same tokens for the same requests: count them once
     return {"tokens": toks, "seconds": float(dt.item()), "latencies": lats,
             "global_batch": batch, "parallelism": f"tp{world}", "data_plane": plane,
-            "ranks_info": infos}
+            "ranks_info": infos, "last_outputs": last}

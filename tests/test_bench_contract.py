@@ -59,6 +59,23 @@ def test_bench_single_cpu():
     assert rec["config"]["global_batch"] == 4
 
 
+def test_bench_dump_outputs(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed wave's token ids (one row per request,
+    float32) and the same arguments give the same array; ``--full`` is accepted and leaves the
+    result line's meaning alone."""
+    import numpy as np
+    cmd = [sys.executable, "bench.py", "--model", "llama-tiny", *COMMON]
+    rec = _run([*cmd, "--dump-outputs", str(tmp_path / "a")])
+    _check(rec, 1, 1, 1, "single")
+    a = np.load(tmp_path / "a" / "output_ids.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 100 - rec["config"]["prompt_len"])
+    assert (a == np.floor(a)).all() and a.min() >= 0
+    rec = _run([*cmd, "--full", "--dump-outputs", str(tmp_path / "b")])
+    _check(rec, 1, 1, 1, "single")
+    assert [p.name for p in (tmp_path / "b").iterdir()] == ["output_ids.npy"]
+    assert np.array_equal(a, np.load(tmp_path / "b" / "output_ids.npy"))
+
+
 @pytest.mark.parametrize("mode,model,par,gb", [
     ("pp", "llama-tiny", "pp2", 12),        # M = N + 1 microbatches of --batch
     ("dp", "llama-tiny", "dp2", 8),
