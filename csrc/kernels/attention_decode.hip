@@ -44,12 +44,23 @@ __device__ __forceinline__ int decode_bt_window(const int* __restrict__ block_ta
   return block_tables[(long)b * max_blocks + min(s_begin / block_size + lane, last_blk)];
 }
 
-// [s_begin, s_end) of wave wv when WPI waves split a context of ctx tokens by whole tiles
+// Sliding window: the query of a decode step sits at position ctx - 1 and sees the keys
+// [max(0, ctx - window), ctx), `window` keys with its own; window <= 0 = full attention. The
+// bound is per sequence and aligned to neither a tile nor a KV block: every kernel form
+// starts its token range (and with it its tiles and its block-table window) there.
+// (Wave-uniform like ctx; readfirstlane puts it, and the tile and block-window counters that
+// start from it, in scalar registers: the 128-VGPR kernels have none to spare.)
+__device__ __forceinline__ int decode_win_lo(int ctx, int window) {
+  return window > 0 ? __builtin_amdgcn_readfirstlane(max(0, ctx - window)) : 0;
+}
+
+// [s_begin, s_end) of wave wv when WPI waves split the tokens [lo, ctx) by whole tiles
 template <int WPI>
-__device__ __forceinline__ void decode_wg_range(int ctx, int wv, int& s_begin, int& s_end) {
-  const int tiles = (ctx + DEC_TILE - 1) / DEC_TILE;
+__device__ __forceinline__ void decode_wg_range(int lo, int ctx, int wv, int& s_begin,
+                                                int& s_end) {
+  const int tiles = (ctx - lo + DEC_TILE - 1) / DEC_TILE;
   const int per = (tiles + WPI - 1) / WPI;
-  s_begin = min(ctx, wv * per * DEC_TILE);
+  s_begin = min(ctx, lo + wv * per * DEC_TILE);
   s_end = min(ctx, s_begin + per * DEC_TILE);
 }
 
@@ -222,7 +233,7 @@ __global__ void __launch_bounds__(256, MINW) decode_attn_kernel(
     const u16* __restrict__ k_cache, const u16* __restrict__ v_cache,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ context_lens,
     int B, int hq, int hkv, int block_size, float scale_log2, int num_splits, int split_tokens,
-    float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+    float* __restrict__ ws_o, float* __restrict__ ws_ml, int window) {
   constexpr int KK = HD / 32;     // MFMA k-steps over head_dim
   constexpr int VROW = HD + 16;   // padded LDS row of the V tile, in u16
   __shared__ __attribute__((aligned(16))) u16 vtile_all[DEC_WAVES][DEC_TILE * VROW];
@@ -238,7 +249,7 @@ __global__ void __launch_bounds__(256, MINW) decode_attn_kernel(
   const int col = lane & 15, grp = lane >> 4;
   const int G = hq / hkv;
   const int ctx = context_lens[b];
-  const int s_begin = split * split_tokens;
+  const int s_begin = decode_win_lo(ctx, window) + split * split_tokens;
   const int s_end = min(ctx, s_begin + split_tokens);
 
   // Q^T fragments (B operand): head = col, dims 32kk + 8grp .. +7
@@ -319,7 +330,7 @@ __global__ void __launch_bounds__(256) decode_attn_wg_kernel(
     u16* __restrict__ out, const u16* __restrict__ q, int q_stride,
     const u16* __restrict__ k_cache, const u16* __restrict__ v_cache,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ context_lens,
-    int B, int hq, int hkv, int block_size, float scale_log2) {
+    int B, int hq, int hkv, int block_size, float scale_log2, int window) {
   constexpr int HD = 128, KK = HD / 32, VROW = HD + 16;
   __shared__ __attribute__((aligned(16))) u16 vtile_all[DEC_WAVES][DEC_TILE * VROW];
   __shared__ float ml_all[DEC_WAVES][16][2];
@@ -340,7 +351,8 @@ __global__ void __launch_bounds__(256) decode_attn_wg_kernel(
     }
   }
   int s_begin, s_end;
-  decode_wg_range<DEC_WAVES>(context_lens[b], wv, s_begin, s_end);
+  const int ctx = context_lens[b];
+  decode_wg_range<DEC_WAVES>(decode_win_lo(ctx, window), ctx, wv, s_begin, s_end);
   const int bt0 = decode_bt_window(block_tables, max_blocks, b, s_begin, s_end, block_size, lane);
   decode_attn_wg<DEC_WAVES>(qf, vtile_all, ml_all, wv, lane, b, kvh, G, s_begin, s_end, bt0,
                             out, k_cache, v_cache, block_tables, max_blocks, hq, hkv,
@@ -368,7 +380,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
     const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ context_lens,
-    int B, int hq, int hkv, int block_size, float scale_log2) {
+    int B, int hq, int hkv, int block_size, float scale_log2, int window) {
   constexpr int HD = 128, HALF = 64, KK = HD / 32, VROW = HD + 16, DB = HD / 16;
   // SPL > 0: src = the QKV GEMM's fp32 split-K slabs [SPL, B, N]; SPL == 0: the bf16 QKV rows
   // [B, N] of an unsplit GEMM (the same prologue minus the slab sum)
@@ -450,8 +462,8 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
   }
   // the block-table window too: every load the tile loop's first tile waits on except the
   // new cache row is issued before the fence below
-  int s_begin = 0, s_end = ctx;
-  if constexpr (WPI > 1) decode_wg_range<WPI>(ctx, wv, s_begin, s_end);
+  int s_begin = decode_win_lo(ctx, window), s_end = ctx;
+  if constexpr (WPI > 1) decode_wg_range<WPI>(s_begin, ctx, wv, s_begin, s_end);
   const int bt0 = decode_bt_window(block_tables, max_blocks, b, s_begin, s_end, block_size, lane);
   // ---- this token's k (rotated) and v -> paged cache (lane: dims lane, lane + 64)
   const int slot = slot_mapping[b];
@@ -496,7 +508,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
   // before those loads
   __threadfence_block();
   if constexpr (WPI == 1) {
-    decode_attn_core<HD>(qf, vt, lane, b, kvh, 0, G, ctx, 0, ctx, out, k_cache, v_cache,
+    decode_attn_core<HD>(qf, vt, lane, b, kvh, 0, G, ctx, s_begin, ctx, out, k_cache, v_cache,
                          block_tables, max_blocks, hq, hkv, block_size, scale_log2, 1, nullptr,
                          nullptr, bt0);
   } else {
@@ -525,7 +537,7 @@ __global__ void __launch_bounds__(256, 2) decode_attn_pipe_kernel(
     const u16* __restrict__ k_cache, const u16* __restrict__ v_cache,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ context_lens,
     int B, int hq, int hkv, int block_size, float scale_log2, int num_splits, int split_tokens,
-    float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+    float* __restrict__ ws_o, float* __restrict__ ws_ml, int window) {
   static_assert(HD == 128, "pipelined decode attention: head_dim 128");
   constexpr int KK = HD / 32, DB = HD / 16;
   constexpr int VT_BYTES = DEC_TILE * HD * 2;                  // 8 KiB per V tile
@@ -545,7 +557,7 @@ __global__ void __launch_bounds__(256, 2) decode_attn_pipe_kernel(
     kvh = bh % hkv;
     b = bh / hkv;
     const int ctx = context_lens[b];
-    sb = split * split_tokens;
+    sb = decode_win_lo(ctx, window) + split * split_tokens;
     se = min(ctx, sb + split_tokens);
   };
   auto ntiles_of = [&](int sb, int se) { return se > sb ? (se - sb + DEC_TILE - 1) / DEC_TILE : 1; };
@@ -802,12 +814,19 @@ static bool wg_form(long items) {
   return g_decode_form == DEC_WAVES || (g_decode_form != 1 && items <= 256);
 }
 
-extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, const void* k_cache,
-                                    const void* v_cache, const int* block_tables, int max_blocks,
-                                    const int* context_lens, int B, int hq, int hkv, int hd,
-                                    int block_size, float scale, int max_context, int num_splits,
-                                    void* workspace, hipStream_t st) {
+// window > 0: sliding-window attention (decode_win_lo); the splits divide the longest span a
+// sequence can have, min(max_context, window) tokens, each offset by its sequence's start,
+// so the work follows the window and no split is empty for every sequence
+extern "C" int dli_decode_attention_win(void* out, const void* q, int q_stride,
+                                        const void* k_cache, const void* v_cache,
+                                        const int* block_tables, int max_blocks,
+                                        const int* context_lens, int B, int hq, int hkv, int hd,
+                                        int block_size, float scale, int max_context,
+                                        int num_splits, void* workspace, int window,
+                                        hipStream_t st) {
   if (B <= 0) return 0;
+  if (window < 0) window = 0;
+  if (window > 0 && window < max_context) max_context = window;
   if (hq % hkv || hq / hkv > 16 || block_size % 16 || (hd != 64 && hd != 128))
     return (int)hipErrorInvalidValue;
   if (num_splits < 1) num_splits = 1;
@@ -830,23 +849,23 @@ extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, cons
     decode_attn_pipe_kernel<128><<<gp, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
         block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml);
+        split_tokens, ws_o, ws_ml, window);
   } else if (hd == 128 && num_splits == 1 && wg_form(items)) {
     decode_attn_wg_kernel<<<(int)items, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
-        block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2);
+        block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window);
   } else {
   dim3 grid((int)((items + DEC_WAVES - 1) / DEC_WAVES));
   if (hd == 128)
     decode_attn_kernel<128, 4><<<grid, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
         block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml);
+        split_tokens, ws_o, ws_ml, window);
   else
     decode_attn_kernel<64, 1><<<grid, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
         block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml);
+        split_tokens, ws_o, ws_ml, window);
   }
   if (num_splits > 1) {
     const long total = (long)B * hq * (hd / 8);
@@ -859,18 +878,31 @@ extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, cons
   DLI_RETURN_LAUNCH();
 }
 
+extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, const void* k_cache,
+                                    const void* v_cache, const int* block_tables, int max_blocks,
+                                    const int* context_lens, int B, int hq, int hkv, int hd,
+                                    int block_size, float scale, int max_context, int num_splits,
+                                    void* workspace, hipStream_t st) {
+  return dli_decode_attention_win(out, q, q_stride, k_cache, v_cache, block_tables, max_blocks,
+                                  context_lens, B, hq, hkv, hd, block_size, scale, max_context,
+                                  num_splits, workspace, 0, st);
+}
+
 // Fused split-K QKV reduce + RoPE + KV-cache write + decode attention (one KV split, head
 // dim 128, RoPE models): ws = the QKV GEMM's fp32 slabs [splits, B, (hq + 2 hkv) * 128], or
 // with splits == 0 the bf16 QKV rows [B, (hq + 2 hkv) * 128] of an unsplit GEMM.
 // fmt: 0 = fp32 slabs (or the bf16 rows when splits == 0), 1 = fp16 x 1/16 slabs (EPI_SLAB16)
-extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
-                                          const int* positions, const int* slot_mapping,
-                                          const float* cos_sin, void* k_cache, void* v_cache,
-                                          const int* block_tables, int max_blocks,
-                                          const int* context_lens, int B, int hq, int hkv,
-                                          int hd, int block_size, float scale, int fmt,
-                                          hipStream_t st) {
+// window > 0: sliding-window attention (decode_win_lo)
+extern "C" int dli_decode_attention_fused_win(void* out, const void* ws, int splits,
+                                              const int* positions, const int* slot_mapping,
+                                              const float* cos_sin, void* k_cache,
+                                              void* v_cache, const int* block_tables,
+                                              int max_blocks, const int* context_lens, int B,
+                                              int hq, int hkv, int hd, int block_size,
+                                              float scale, int fmt, int window,
+                                              hipStream_t st) {
   if (B <= 0) return 0;
+  if (window < 0) window = 0;
   if (hd != 128 || hq % hkv || hq / hkv > 16 || block_size % 16 ||
       (splits != 0 && splits != 2 && splits != 4) || fmt < 0 || fmt > 1 ||
       (fmt == 1 && splits == 0))
@@ -882,7 +914,7 @@ extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
   dim3 grid((int)(per_wg ? items : (items + DEC_WAVES - 1) / DEC_WAVES));
 #define DLI_DAF(S, W, F) decode_attn_fused_kernel<S, W, F><<<grid, 64 * DEC_WAVES, 0, st>>>(   \
       (u16*)out, ws, N, positions, slot_mapping, cos_sin, (u16*)k_cache, (u16*)v_cache,      \
-      block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2)
+      block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window)
   if (per_wg) {
     if (splits == 0) DLI_DAF(0, DEC_WAVES, false);
     else if (splits == 2) { if (fmt) DLI_DAF(2, DEC_WAVES, true); else DLI_DAF(2, DEC_WAVES, false); }
@@ -894,6 +926,19 @@ extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
   }
 #undef DLI_DAF
   DLI_RETURN_LAUNCH();
+}
+
+extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
+                                          const int* positions, const int* slot_mapping,
+                                          const float* cos_sin, void* k_cache, void* v_cache,
+                                          const int* block_tables, int max_blocks,
+                                          const int* context_lens, int B, int hq, int hkv,
+                                          int hd, int block_size, float scale, int fmt,
+                                          hipStream_t st) {
+  return dli_decode_attention_fused_win(out, ws, splits, positions, slot_mapping, cos_sin,
+                                        k_cache, v_cache, block_tables, max_blocks,
+                                        context_lens, B, hq, hkv, hd, block_size, scale, fmt, 0,
+                                        st);
 }
 
 extern "C" long dli_decode_attention_workspace_bytes(int B, int hq, int hd, int num_splits) {

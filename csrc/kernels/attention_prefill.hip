@@ -19,12 +19,18 @@
 // (rope_cache), so keys come from the cache through the block table: a chunk of len queries
 // at positions [ctx - len, ctx) attends over all ctx cached keys of its sequence (earlier
 // chunks, a recomputed prefix) with the causal bound shifted by ctx - len.
+// Sliding window (window > 0): query q sees the keys q - window < j <= q, `window` keys with
+// its own. A workgroup starts at the 64-key tile that holds the first key of its first row,
+// a wave skips the tiles wholly below its own first row's window as it skips those above its
+// rows, and the tiles a window edge crosses are masked per (query, key). A row's own key is
+// always visible, so no row has an empty window.
 // Grid: (ceil(max_len / (16 wph)), num_seqs, Hq * wph / 4). wph = waves per query head: 4
 // (64 rows per workgroup) in general; for batches of short prompts (max_len <= 32 / 16) a
 // workgroup packs 2 / 4 query heads of one GQA group (2 / 1 waves each): the K/V tiles it
 // stages serve every packed head, and no wave idles past a 32-token prompt (the bench's
 // 512 x 32-token prefill ran 16,384 half-idle workgroups).
 #include "common.h"
+#include <limits.h>
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -40,7 +46,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     const int* __restrict__ cu_seqlens, int hq, int hkv, float scale_log2,
     const int* __restrict__ ctx_lens, const u16* __restrict__ k_cache,
     const u16* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
-    int block_size, int wph) {
+    int block_size, int wph, int window) {
   constexpr int KK = HD / 32, DB = HD / 16;
   // K row in LDS (u16): 288 B for hd 128 (72 dwords; 40 for hd 64). With the
   // ds_read_b128 lane groups of gfx950 ({0-3,12-15,20-27}, ... MI355X_MICROARCH.md §LDS)
@@ -86,6 +92,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   for (int i = 0; i < DB; ++i) o_acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int kend_wg = min(nkeys, qoff + wg_q0 + wph * PF_QROWS);       // last row's bound
   const int kend_w = min(nkeys, qoff + q0 + PF_QROWS);                 // this wave's bound
+  // window: keys > (query position) - wspan; off = a span no key reaches
+  const int wspan = window > 0 ? window : INT_MAX;
+  const int kbeg_w = max(0, qoff + q0 - wspan + 1);                    // this wave's first key
+  const int kbeg_wg = max(0, qoff + wg_q0 - wspan + 1) / PF_KT * PF_KT;   // first tile staged
 
   // the next K/V tile in flight in registers: named values, not arrays — uint4 kreg[PER]
   // indexed in a loop was promoted to LDS by the compiler (a second staging copy through
@@ -121,9 +131,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     *reinterpret_cast<uint4*>(ktile + r * KROW + c * 8) = kr;
     *reinterpret_cast<uint4*>(vtile + r * VROW + c * 8) = vr;
   };
-  load_tile(0);
+  load_tile(kbeg_wg);
   const int qrow = (lane >> 2) & 3, pcol = lane & 3;
-  for (int k0 = 0; k0 < kend_wg; k0 += PF_KT) {
+  for (int k0 = kbeg_wg; k0 < kend_wg; k0 += PF_KT) {
     __syncthreads();                                             // previous tile fully read
     store1(0, kr0, vr0);
     store1(1, kr1, vr1);
@@ -133,7 +143,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     }
     __syncthreads();                                             // tile visible to all waves
     if (k0 + PF_KT < kend_wg) load_tile(k0 + PF_KT);             // in flight during compute
-    if (!active || k0 >= kend_w) continue;                       // tile above this wave's rows
+    // tile above this wave's rows, or wholly below their window
+    if (!active || k0 >= kend_w || k0 + PF_KT <= kbeg_w) continue;
     // ---- S^T = K . Q^T over four 16-key subtiles
     f32x4 s_acc[4];
 #pragma unroll
@@ -151,7 +162,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + 16 * s + 4 * grp + r;
-        const float v = (key <= my_q && key < nkeys) ? s_acc[s][r] * scale_log2 : -INFINITY;
+        const float v = (key <= my_q && key < nkeys && key > my_q - wspan)
+                            ? s_acc[s][r] * scale_log2 : -INFINITY;
         p[s * 4 + r] = v;
         tmax = fmaxf(tmax, v);
       }
@@ -254,7 +266,7 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
     const int* __restrict__ cu_seqlens, int hq, int hkv, float scale_log2,
     const int* __restrict__ ctx_lens, const u16* __restrict__ k_cache,
     const u16* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride,
-    int block_size) {
+    int block_size, int window) {
   static_assert(HD == 128, "long-sequence kernel: head_dim 128");
   constexpr int KC = HD / 16;                      // K-steps of the QK^T product
   constexpr int DBK = HD / 32;                     // 32-wide d blocks of O^T
@@ -295,6 +307,11 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
   const int wq_lo = qoff + q0, wq_hi = qoff + min(q0 + PL_QROWS, len) - 1;
   const int kend_wg = min(nkeys, qoff + min(wg_q0 + PL_ROWS, len));
   const int ntiles = (kend_wg + PL_KT - 1) / PL_KT;
+  // window: keys > (query position) - wspan; off = a span no key reaches. The workgroup's
+  // first tile holds the first key of its first row; a wave's first key is that of its own
+  const int wspan = window > 0 ? window : INT_MAX;
+  const int tfirst = max(0, qoff + wg_q0 - wspan + 1) / PL_KT;
+  const int kbeg_w = max(0, wq_lo - wspan + 1);
 
   f32x16 o[DBK];
 #pragma unroll
@@ -333,9 +350,9 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
     }
   };
 
-  stage(0, 0);
-  if (ntiles > 1) {
-    stage(1, PL_KT);
+  stage(0, tfirst * PL_KT);
+  if (ntiles - tfirst > 1) {
+    stage(1, (tfirst + 1) * PL_KT);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             // tile 0 landed
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -360,10 +377,10 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
   // work with the MFMAs.)
   f32x16 sacc[2];
   int cur = 0;
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = tfirst; t < ntiles; ++t) {
     const int k0 = t * PL_KT;
     if (t + 2 < ntiles) stage(cur == 0 ? 2 : cur - 1, k0 + 2 * PL_KT);
-    if (active && k0 <= wq_hi) {
+    if (active && k0 <= wq_hi && k0 + PL_KT > kbeg_w) {
       const char* kt = lds[cur][0];
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
@@ -377,14 +394,14 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
           sacc[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[c], sacc[sub], 0, 0, 0);
         }
       }
-      // mask (only tiles crossing this wave's diagonal or the key end)
-      if (k0 + PL_KT - 1 > wq_lo || k0 + PL_KT > nkeys) {
+      // mask (only tiles crossing this wave's diagonal, the key end or a window's lower edge)
+      if (k0 + PL_KT - 1 > wq_lo || k0 + PL_KT > nkeys || k0 <= wq_hi - wspan) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + 32 * sub + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (key > qpos || key >= nkeys) sacc[sub][r] = -INFINITY;
+            if (key > qpos || key >= nkeys || key <= qpos - wspan) sacc[sub][r] = -INFINITY;
           }
       }
       float mloc = pl_max3(sacc[0][0], sacc[0][1], sacc[0][2]);
@@ -470,15 +487,16 @@ static int launch_prefill(void* out, int out_stride, const void* qkv, int row_st
                           const int* cu_seqlens, int num_seqs, int max_seqlen, int hq, int hkv,
                           int hd, float scale, const int* ctx_lens, const void* k_cache,
                           const void* v_cache, const int* block_tables, int bt_stride,
-                          int block_size, hipStream_t st) {
+                          int block_size, int window, hipStream_t st) {
   if (num_seqs <= 0 || max_seqlen <= 0) return 0;
+  if (window < 0) window = 0;
   if (hq % hkv || (hd != 64 && hd != 128)) return (int)hipErrorInvalidValue;
   const float sl2 = scale * 1.4426950408889634f;
   if (hd == 128 && max_seqlen >= g_pl_min_len) {     // long sequences: 256-row workgroups
     dim3 grid32((max_seqlen + PL_ROWS - 1) / PL_ROWS, num_seqs, hq);
     prefill_attn32_kernel<128, PAGED><<<grid32, 512, 0, st>>>(
         (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size);
+        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, window);
     DLI_RETURN_LAUNCH();
   }
   // waves per query head: pack 2 / 4 heads of one GQA group into a workgroup for short
@@ -492,24 +510,48 @@ static int launch_prefill(void* out, int out_stride, const void* qkv, int row_st
   if (hd == 128)
     prefill_attn_kernel<128, PAGED><<<grid, 256, 0, st>>>(
         (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph);
+        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph,
+        window);
   else
     prefill_attn_kernel<64, PAGED><<<grid, 256, 0, st>>>(
         (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph);
+        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph,
+        window);
   DLI_RETURN_LAUNCH();
+}
+
+// window > 0: sliding-window attention (query q sees keys q - window < j <= q)
+extern "C" int dli_prefill_attention_win(void* out, int out_stride, const void* qkv,
+                                         int row_stride, const int* cu_seqlens, int num_seqs,
+                                         int max_seqlen, int hq, int hkv, int hd, float scale,
+                                         int window, hipStream_t st) {
+  return launch_prefill<false>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
+                               max_seqlen, hq, hkv, hd, scale, nullptr, nullptr, nullptr,
+                               nullptr, 0, 16, window, st);
 }
 
 extern "C" int dli_prefill_attention(void* out, int out_stride, const void* qkv, int row_stride,
                                      const int* cu_seqlens, int num_seqs, int max_seqlen, int hq,
                                      int hkv, int hd, float scale, hipStream_t st) {
-  return launch_prefill<false>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
-                               max_seqlen, hq, hkv, hd, scale, nullptr, nullptr, nullptr,
-                               nullptr, 0, 16, st);
+  return dli_prefill_attention_win(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
+                                   max_seqlen, hq, hkv, hd, scale, 0, st);
 }
 
 // Chunked prefill: q from qkv rows [cu[s], cu[s+1]); keys 0..ctx_lens[s]-1 of sequence s
 // from the paged caches [num_blocks, hkv, block_size, hd] through block_tables[s, :].
+extern "C" int dli_prefill_attention_paged_win(void* out, int out_stride, const void* qkv,
+                                               int row_stride, const int* cu_seqlens,
+                                               const int* ctx_lens, const void* k_cache,
+                                               const void* v_cache, const int* block_tables,
+                                               int bt_stride, int num_seqs, int max_seqlen,
+                                               int hq, int hkv, int hd, int block_size,
+                                               float scale, int window, hipStream_t st) {
+  if (block_size <= 0) return (int)hipErrorInvalidValue;
+  return launch_prefill<true>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
+                              max_seqlen, hq, hkv, hd, scale, ctx_lens, k_cache, v_cache,
+                              block_tables, bt_stride, block_size, window, st);
+}
+
 extern "C" int dli_prefill_attention_paged(void* out, int out_stride, const void* qkv,
                                            int row_stride, const int* cu_seqlens,
                                            const int* ctx_lens, const void* k_cache,
@@ -517,10 +559,9 @@ extern "C" int dli_prefill_attention_paged(void* out, int out_stride, const void
                                            int bt_stride, int num_seqs, int max_seqlen, int hq,
                                            int hkv, int hd, int block_size, float scale,
                                            hipStream_t st) {
-  if (block_size <= 0) return (int)hipErrorInvalidValue;
-  return launch_prefill<true>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
-                              max_seqlen, hq, hkv, hd, scale, ctx_lens, k_cache, v_cache,
-                              block_tables, bt_stride, block_size, st);
+  return dli_prefill_attention_paged_win(out, out_stride, qkv, row_stride, cu_seqlens, ctx_lens,
+                                         k_cache, v_cache, block_tables, bt_stride, num_seqs,
+                                         max_seqlen, hq, hkv, hd, block_size, scale, 0, st);
 }
 
 // 0 / 1: head packing of the short-prompt kernel off / on; returns the previous setting

@@ -35,6 +35,9 @@ class ModelConfig:
     # HF ``rope_scaling`` as sorted (key, value) pairs: () = none; rope_type "llama3"
     # (Llama-3.1 / 3.2 checkpoints: low-frequency inv_freq rescaled) or "linear"
     rope_scaling: tuple = ()
+    # sliding-window attention (Mistral): a query sees the last ``sliding_window`` keys up to
+    # and including its own, in every layer; 0 = full attention
+    sliding_window: int = 0
 
     @property
     def is_moe(self) -> bool:
@@ -114,6 +117,13 @@ MIXTRAL_8X7B = ModelConfig(
     max_position=32768, rope_theta=1e6, norm_eps=1e-5, num_experts=8, top_k_experts=2,
     bos_token_id=1, eos_token_id=2)
 
+# Mistral-7B-v0.1: Llama layers, every one with a 4096-key sliding window
+MISTRAL_7B = ModelConfig(
+    name="mistral-7b", arch="llama", hidden_size=4096, num_layers=32, num_heads=32,
+    num_kv_heads=8, head_dim=128, intermediate_size=14336, vocab_size=32000,
+    max_position=32768, rope_theta=10000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2,
+    sliding_window=4096)
+
 # Tiny variants: same code paths, test-sized. Shapes keep the hardware-friendly
 # multiples (head_dim 64/128, hidden multiple of 256) so HIP kernels see real layouts.
 LLAMA_TINY = ModelConfig(
@@ -123,6 +133,10 @@ LLAMA_TINY = ModelConfig(
 
 LLAMA_TINY128 = replace(LLAMA_TINY, name="llama-tiny128", hidden_size=512, num_heads=4,
                         num_kv_heads=2, head_dim=128, intermediate_size=1024)
+
+# sliding-window twins (head dim 64 / 128): a window short enough for tests to cross
+MISTRAL_TINY = replace(LLAMA_TINY, name="mistral-tiny", sliding_window=24)
+MISTRAL_TINY128 = replace(LLAMA_TINY128, name="mistral-tiny128", sliding_window=24)
 
 # 8 layers: one per stage of an 8-rank pipeline test
 LLAMA_TINY8 = replace(LLAMA_TINY, name="llama-tiny8", num_layers=8)
@@ -139,7 +153,8 @@ GPT2_TINY = replace(GPT2, name="gpt2-tiny", hidden_size=256, num_layers=2, num_h
 
 _REGISTRY = {c.name: c for c in
              (GPT2, LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, LLAMA_TINY, LLAMA_TINY128,
-              LLAMA_TINY8, MIXTRAL_TINY, MIXTRAL_TINY8E, GPT2_TINY)}
+              LLAMA_TINY8, MIXTRAL_TINY, MIXTRAL_TINY8E, GPT2_TINY, MISTRAL_7B, MISTRAL_TINY,
+              MISTRAL_TINY128)}
 
 _ALIASES = {
     "openai-community/gpt2": "gpt2",
@@ -151,6 +166,8 @@ _ALIASES = {
     "meta-llama/meta-llama-3-70b": "llama3-70b",
     "llama-3-70b": "llama3-70b",
     "llama3_70b": "llama3-70b",
+    "mistralai/mistral-7b-v0.1": "mistral-7b",
+    "mistral_7b": "mistral-7b",
     "mistralai/mixtral-8x7b-v0.1": "mixtral-8x7b",
     "mixtral": "mixtral-8x7b",
     "mixtral_8x7b": "mixtral-8x7b",

@@ -58,8 +58,13 @@ def find_hf_dir(root: str, name: str) -> Optional[Path]:
     return None
 
 
-def config_from_hf(c: dict, name: Optional[str] = None) -> ModelConfig:
-    """Map a HF ``config.json`` (llama / mistral / mixtral / gpt2 model types)."""
+def config_from_hf(c: dict, name: Optional[str] = None,
+                   sliding_window: bool = False) -> ModelConfig:
+    """Map a HF ``config.json`` (llama / mistral / mixtral / gpt2 model types).
+    ``sliding_window``: the caller runs the model through ``TransformerLM``, whose attention
+    honours ``ModelConfig.sliding_window``: a checkpoint's window (smaller than its
+    ``max_position_embeddings``) is kept and the context is the model's own. Without it the
+    result describes a full-attention model, so the context is capped at the window."""
     mt = c.get("model_type", "")
     name = name or c.get("_name_or_path") or mt
     if mt == "gpt2":
@@ -89,15 +94,22 @@ def config_from_hf(c: dict, name: Optional[str] = None) -> ModelConfig:
         import torch as _t
         rope_scaled_inv_freq(_t.ones(2, dtype=_t.float64), sc)     # refuse unknown types now
     max_pos = int(c.get("max_position_embeddings", 8192))
-    # sliding-window attention (Mistral): full attention equals it while a sequence fits the
-    # window, so the model's context is capped there instead of silently diverging past it
+    # sliding-window attention (Mistral). A null window, or one the context never outgrows,
+    # is full attention. A caller that does not opt in gets a full-attention config: full
+    # attention equals the windowed one while a sequence fits the window, so the context is
+    # capped there instead of silently diverging past it
     sw = c.get("sliding_window")
+    window = 0
     if sw and int(sw) < max_pos:
-        import logging
-        logging.getLogger(__name__).warning(
-            "sliding_window=%s < max_position_embeddings=%s: context capped at the window "
-            "(sliding-window attention is not implemented)", sw, max_pos)
-        max_pos = int(sw)
+        if sliding_window:
+            window = int(sw)
+        else:
+            import logging
+            logging.getLogger(__name__).warning(
+                "sliding_window=%s < max_position_embeddings=%s: context capped at the window "
+                "(this caller did not ask for sliding-window attention; pass "
+                "sliding_window=True to config_from_hf to serve the full context)", sw, max_pos)
+            max_pos = int(sw)
     return ModelConfig(
         name=name, arch="llama", hidden_size=d, num_layers=int(c["num_hidden_layers"]),
         num_heads=nh, num_kv_heads=int(c.get("num_key_value_heads") or nh),
@@ -110,7 +122,8 @@ def config_from_hf(c: dict, name: Optional[str] = None) -> ModelConfig:
         num_experts=int(c.get("num_local_experts", 0)) if mt == "mixtral" else 0,
         top_k_experts=int(c.get("num_experts_per_tok", 2)),
         tie_embeddings=bool(c.get("tie_word_embeddings", False)),
-        bos_token_id=int(c.get("bos_token_id") or 1), eos_token_id=_eos(c, 2))
+        bos_token_id=int(c.get("bos_token_id") or 1), eos_token_id=_eos(c, 2),
+        sliding_window=window)
 
 
 def _eos(c: dict, default: int) -> int:
@@ -166,7 +179,8 @@ def load_hf_dir(d, device="cpu", dtype=torch.bfloat16, name: Optional[str] = Non
     """(config, our parameter dict on ``device``) from a HF checkpoint directory; with
     ``layers`` / ``first`` / ``last`` only that pipeline stage's tensors."""
     d = Path(d)
-    cfg = config_from_hf(json.loads((d / "config.json").read_text()), name)
+    cfg = config_from_hf(json.loads((d / "config.json").read_text()), name,
+                         sliding_window=True)
     sd = LazyStateDict(d)
     try:
         params = from_hf_state_dict(cfg, sd, layers=layers, first=first, last=last, dtype=dtype)

@@ -155,7 +155,8 @@ class TransformerLM:
                 attn = ops.linear_rope_attention(h, lp["wqkv"], b.positions, b.slot_mapping,
                                                  self.cos_sin, kc, vc, b.block_tables,
                                                  b.context_lens, b.max_context, cfg.num_heads,
-                                                 cfg.num_kv_heads, cfg.head_dim, self.scale)
+                                                 cfg.num_kv_heads, cfg.head_dim, self.scale,
+                                                 window=cfg.sliding_window)
             if attn is None:
                 qkv = ops.linear_rope_cache(h, lp["wqkv"], b.positions, b.slot_mapping,
                                             self.cos_sin, kc, vc, cfg.num_heads,
@@ -197,6 +198,7 @@ class TransformerLM:
 
     def _attend(self, qkv, b: DeviceBatch, kc, vc) -> torch.Tensor:
         cfg = self.cfg
+        win = cfg.sliding_window                 # 0 = full attention
         if b.is_prefill:
             if b.num_decode:                     # mixed step: decode rows, then prefill chunks
                 nd = b.num_decode
@@ -204,22 +206,25 @@ class TransformerLM:
                                   dtype=qkv.dtype, device=qkv.device)
                 ops.decode_attention(qkv[:nd], kc, vc, b.block_tables[:nd],
                                      b.context_lens[:nd], b.max_context_decode, cfg.num_heads,
-                                     cfg.num_kv_heads, cfg.head_dim, self.scale, out=out[:nd])
+                                     cfg.num_kv_heads, cfg.head_dim, self.scale, out=out[:nd],
+                                     window=win)
                 ops.prefill_attention_paged(qkv[nd:], b.cu_seqlens_prefill,
                                             b.max_seqlen_prefill, b.context_lens[nd:],
                                             b.block_tables[nd:], kc, vc, cfg.num_heads,
                                             cfg.num_kv_heads, cfg.head_dim, self.scale,
-                                            out=out[nd:])
+                                            out=out[nd:], window=win)
                 return out
             if b.block_tables is not None:       # chunked prefill over the paged cache
                 return ops.prefill_attention_paged(qkv, b.cu_seqlens, b.max_seqlen,
                                                    b.context_lens, b.block_tables, kc, vc,
                                                    cfg.num_heads, cfg.num_kv_heads,
-                                                   cfg.head_dim, self.scale)
+                                                   cfg.head_dim, self.scale, window=win)
             return ops.prefill_attention(qkv, b.cu_seqlens, b.max_seqlen, cfg.num_heads,
-                                         cfg.num_kv_heads, cfg.head_dim, self.scale)
+                                         cfg.num_kv_heads, cfg.head_dim, self.scale,
+                                         window=win)
         return ops.decode_attention(qkv, kc, vc, b.block_tables, b.context_lens, b.max_context,
-                                    cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, self.scale)
+                                    cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, self.scale,
+                                    window=win)
 
     def _attention(self, qkv, b: DeviceBatch, kc, vc) -> torch.Tensor:
         cfg = self.cfg

@@ -370,14 +370,17 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
 
 
 def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache,
-                          block_tables, context_lens, max_context: int, hq, hkv, hd, scale):
+                          block_tables, context_lens, max_context: int, hq, hkv, hd, scale,
+                          window: int = 0):
     """Decode step, one fused pass after the QKV GEMM: the split-K slabs (or, for an unsplit
     plan, the bf16 QKV rows) are reduced, q and k rotated, k/v written to the paged cache and
     attention computed by ONE kernel per layer (``dli_decode_attention_fused``) instead of
     ``linear_rope_cache`` + ``decode_attention``. Returns the attention output [B, hq*hd], or
     None where the fused kernel does not apply (the caller then runs the two-kernel path):
     split counts other than 2 / 4, KV-split attention (long contexts at small batch), the
-    pipelined long-context kernel, head dim != 128."""
+    pipelined long-context kernel, head dim != 128. ``window`` > 0: sliding-window attention;
+    the choice between the kernels follows the span a sequence can attend over,
+    min(max_context, window)."""
     xr = x.residual if isinstance(x, NormedRows) else x
     if hd != 128 or k_cache is None or not _use_native(xr):
         return None
@@ -385,10 +388,11 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     if p is not None and p.splits not in (2, 4):
         return None
     B, K = x.shape
-    if decode_num_splits(B, hkv, max_context) != 1:
+    span = decode_span(max_context, window)
+    if decode_num_splits(B, hkv, span) != 1:
         return None
     mode = int(N.require_native().dli_decode_get_pipe())
-    if mode == 1 or (mode == 2 and -(-max_context // 32) * 32 >= 768):
+    if mode == 1 or (mode == 2 and -(-span // 32) * 32 >= 768):
         return None                       # dli_decode_attention picks the pipelined kernel
     Nn = w.shape[0]
     fmt = 0
@@ -402,10 +406,10 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
                 x = x.materialize()
             fmt = _slab_gemm(x, w, p, src)
     out = torch.empty(B, hq * hd, dtype=x.dtype, device=x.device)
-    _native_call("dli_decode_attention_fused", _p(out), _p(src), splits, _p(positions),
+    _native_call("dli_decode_attention_fused_win", _p(out), _p(src), splits, _p(positions),
                  _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), _p(block_tables),
                  block_tables.stride(0), _p(context_lens), B, hq, hkv, hd, k_cache.shape[2],
-                 scale, fmt, _st())
+                 scale, fmt, max(int(window), 0), _st())
     return out
 
 
@@ -474,12 +478,16 @@ def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, 
 
 
 # ----------------------------------------------------------------------------- attention
-def prefill_attention(qkv, cu_seqlens, max_seqlen: int, hq, hkv, hd, scale, out=None):
-    """Causal varlen attention over the packed prompt tokens in ``qkv``; returns [T, Hq*hd]."""
+def prefill_attention(qkv, cu_seqlens, max_seqlen: int, hq, hkv, hd, scale, out=None,
+                      window: int = 0):
+    """Causal varlen attention over the packed prompt tokens in ``qkv``; returns [T, Hq*hd].
+    ``window`` > 0: sliding-window attention (the query at position p sees the keys
+    p - window < j <= p); 0 = full attention."""
+    window = max(int(window), 0)
     T = qkv.shape[0]
     if not _use_native(qkv):
         q, k, v = R.split_qkv(qkv, hq, hkv, hd)
-        o = R.prefill_attention(q, k, v, cu_seqlens, scale).reshape(T, hq * hd)
+        o = R.prefill_attention(q, k, v, cu_seqlens, scale, window).reshape(T, hq * hd)
         if out is not None:
             out.copy_(o)
             return out
@@ -487,8 +495,8 @@ def prefill_attention(qkv, cu_seqlens, max_seqlen: int, hq, hkv, hd, scale, out=
     if out is None:
         out = torch.empty(T, hq * hd, dtype=qkv.dtype, device=qkv.device)
     nseq = cu_seqlens.shape[0] - 1
-    _native_call("dli_prefill_attention", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
-                 _p(cu_seqlens), nseq, max_seqlen, hq, hkv, hd, scale, _st())
+    _native_call("dli_prefill_attention_win", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
+                 _p(cu_seqlens), nseq, max_seqlen, hq, hkv, hd, scale, window, _st())
     return out
 
 
@@ -520,15 +528,17 @@ def prefill_set_pack(on: bool) -> bool:
 
 
 def prefill_attention_paged(qkv, cu_seqlens, max_seqlen: int, context_lens, block_tables,
-                            k_cache, v_cache, hq, hkv, hd, scale, out=None):
+                            k_cache, v_cache, hq, hkv, hd, scale, out=None, window: int = 0):
     """Chunked prefill attention: each sequence's chunk of queries (packed rows of ``qkv``)
     attends over all ``context_lens[i]`` keys of the sequence in the paged cache — earlier
-    chunks plus this one (already written by ``rope_and_cache``); [T, Hq*hd]."""
+    chunks plus this one (already written by ``rope_and_cache``); [T, Hq*hd]. ``window`` > 0:
+    each query sees the last ``window`` keys up to its own position."""
+    window = max(int(window), 0)
     T = qkv.shape[0]
     if not _use_native(qkv):
         q = qkv[:, : hq * hd].reshape(T, hq, hd)
         o = R.prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens,
-                                      block_tables, scale).reshape(T, hq * hd)
+                                      block_tables, scale, window).reshape(T, hq * hd)
         if out is not None:
             out.copy_(o)
             return out
@@ -536,16 +546,22 @@ def prefill_attention_paged(qkv, cu_seqlens, max_seqlen: int, context_lens, bloc
     if out is None:
         out = torch.empty(T, hq * hd, dtype=qkv.dtype, device=qkv.device)
     nseq = cu_seqlens.shape[0] - 1
-    _native_call("dli_prefill_attention_paged", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
-                 _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache), _p(block_tables),
-                 block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd, k_cache.shape[2], scale,
-                 _st())
+    _native_call("dli_prefill_attention_paged_win", _p(out), out.stride(0), _p(qkv),
+                 qkv.stride(0), _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache),
+                 _p(block_tables), block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd,
+                 k_cache.shape[2], scale, window, _st())
     return out
+
+
+def decode_span(max_context: int, window: int = 0) -> int:
+    """The most keys a decode query attends over: the context, or the sliding window."""
+    return min(max_context, window) if window > 0 else max_context
 
 
 def decode_num_splits(B: int, hkv: int, max_context: int) -> int:
     """KV splits so that the B*Hkv*splits work items (one wave each) fill the chip's ~2048
-    resident waves for long contexts, keeping >= 128 tokens per split."""
+    resident waves for long contexts, keeping >= 128 tokens per split. With a sliding window
+    pass the span (``decode_span``): the splits divide the window, not the context."""
     items = B * hkv
     splits = 1
     # tiny batches (batch-1 latency): >= 512 tokens per split, so graphs captured for a
@@ -559,13 +575,17 @@ def decode_num_splits(B: int, hkv: int, max_context: int) -> int:
 
 
 def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_context: int,
-                     hq, hkv, hd, scale, out=None, num_splits: Optional[int] = None):
-    """One query per row of ``qkv`` (rows = sequences) against its paged KV; [B, Hq*hd]."""
+                     hq, hkv, hd, scale, out=None, num_splits: Optional[int] = None,
+                     window: int = 0):
+    """One query per row of ``qkv`` (rows = sequences) against its paged KV; [B, Hq*hd].
+    ``window`` > 0: sliding-window attention, sequence b attends over the keys
+    [max(0, context_lens[b] - window), context_lens[b])."""
     B = qkv.shape[0]
+    window = max(int(window), 0)
     if not _use_native(qkv):
         q = qkv[:, : hq * hd].reshape(B, hq, hd)
         o = R.decode_attention(q, k_cache, v_cache, block_tables, context_lens,
-                               scale).reshape(B, hq * hd)
+                               scale, window).reshape(B, hq * hd)
         if out is not None:
             out.copy_(o)
             return out
@@ -573,15 +593,15 @@ def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_cont
     if out is None:
         out = torch.empty(B, hq * hd, dtype=qkv.dtype, device=qkv.device)
     if num_splits is None:
-        num_splits = decode_num_splits(B, hkv, max_context)
+        num_splits = decode_num_splits(B, hkv, decode_span(max_context, window))
     ws = None
     if num_splits > 1:
         nbytes = B * hq * num_splits * (hd + 2) * 4
         ws = G.workspace(qkv.device, nbytes)
     bs = k_cache.shape[2]
-    _native_call("dli_decode_attention", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
+    _native_call("dli_decode_attention_win", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
                  _p(v_cache), _p(block_tables), block_tables.stride(0), _p(context_lens), B, hq,
-                 hkv, hd, bs, scale, max_context, num_splits, _p(ws), _st())
+                 hkv, hd, bs, scale, max_context, num_splits, _p(ws), window, _st())
     return out
 
 

@@ -40,8 +40,10 @@ _SIGS = {
     "dli_feed_ids": [P, P, P, I, I, P],
     "dli_prefetch": [P, L, I, P, P],
     "dli_decode_attention": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, P],
+    "dli_decode_attention_win": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, P],
     "dli_decode_attention_workspace_bytes": [I, I, I, I],
     "dli_prefill_attention": [P, I, P, I, P, I, I, I, I, I, F, P],
+    "dli_prefill_attention_win": [P, I, P, I, P, I, I, I, I, I, F, I, P],
     "dli_prefill_set_min_len": [I],
     "dli_prefill_set_pack": [I],
     "dli_sample_set_split_max_b": [I],
@@ -51,6 +53,8 @@ _SIGS = {
     "dli_gemm_set_slab_store": [I],
     "dli_gemm_set_slab_store_family": [I, I],
     "dli_prefill_attention_paged": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
+    "dli_prefill_attention_paged_win": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I,
+                                        P],
     "dli_sample": [P, P, L, I, I, P, P, P, P, P, P],
     "dli_sample_workspace_bytes": [I, I],
     "dli_sample_bf16": [P, P, L, I, I, P, P, P, P, P, P],
@@ -61,6 +65,8 @@ _SIGS = {
     "dli_gemv_fused": [P, I, P, F, P, I, P, I, I, I, I, I, I, I, P, P],
     "dli_splitk_rope_cache": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P],
     "dli_decode_attention_fused": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, P],
+    "dli_decode_attention_fused_win": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
+                                       P],
     "dli_moe_route": [P, P, P, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

@@ -188,8 +188,11 @@ def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache,
 
 
 # ----------------------------------------------------------------------------- attention (K7, K8)
-def prefill_attention(q, k, v, cu_seqlens: torch.Tensor, scale: float) -> torch.Tensor:
-    """Causal varlen GQA attention. q [T,Hq,hd], k/v [T,Hkv,hd] -> [T,Hq,hd]."""
+def prefill_attention(q, k, v, cu_seqlens: torch.Tensor, scale: float,
+                      window: int = 0) -> torch.Tensor:
+    """Causal varlen GQA attention. q [T,Hq,hd], k/v [T,Hkv,hd] -> [T,Hq,hd].
+    ``window`` > 0: sliding-window attention, the query at position p sees the keys
+    p - window < j <= p (``window`` keys with its own; the HF Mistral rule); 0 = full."""
     out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     hq, hkv = q.shape[1], k.shape[1]
     rep = hq // hkv
@@ -204,6 +207,8 @@ def prefill_attention(q, k, v, cu_seqlens: torch.Tensor, scale: float) -> torch.
         sc = (qs @ ks.transpose(1, 2)) * scale
         L = e - s
         mask = torch.ones(L, L, dtype=torch.bool, device=q.device).triu(1)
+        if window > 0:
+            mask |= torch.ones(L, L, dtype=torch.bool, device=q.device).tril(-window)
         sc = sc.masked_fill(mask, float("-inf"))
         o = sc.softmax(-1) @ vs
         out[s:e] = o.transpose(0, 1).to(q.dtype)
@@ -221,9 +226,10 @@ def gather_kv(k_cache, v_cache, block_table: torch.Tensor, ctx_len: int):
 
 
 def prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens, block_tables,
-                            scale: float) -> torch.Tensor:
+                            scale: float, window: int = 0) -> torch.Tensor:
     """Chunked prefill: the queries q[cu[i]:cu[i+1]] sit at positions [ctx-L, ctx) of
-    sequence i and attend causally over its ctx = context_lens[i] cached keys."""
+    sequence i and attend causally over its ctx = context_lens[i] cached keys (``window``
+    > 0: over the last ``window`` of them up to their own position, as ``prefill_attention``)."""
     out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     hq, hkv = q.shape[1], k_cache.shape[1]
     rep = hq // hkv
@@ -239,14 +245,19 @@ def prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens, block
         qs = q[s:e].float().transpose(0, 1)                          # [Hq, L, hd]
         sc = (qs @ kk.transpose(1, 2)) * scale                       # [Hq, L, ctx]
         qpos = torch.arange(ctx - L, ctx, device=q.device).unsqueeze(1)
-        mask = torch.arange(ctx, device=q.device).unsqueeze(0) > qpos
+        kpos = torch.arange(ctx, device=q.device).unsqueeze(0)
+        mask = kpos > qpos
+        if window > 0:
+            mask = mask | (kpos <= qpos - window)
         sc = sc.masked_fill(mask, float("-inf"))
         out[s:e] = (sc.softmax(-1) @ vv).transpose(0, 1).to(q.dtype)
     return out
 
 
-def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale) -> torch.Tensor:
-    """q [B,Hq,hd] single query per sequence against its paged cache."""
+def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale,
+                     window: int = 0) -> torch.Tensor:
+    """q [B,Hq,hd] single query per sequence against its paged cache. ``window`` > 0: the
+    query sits at position L - 1 and sees the keys [max(0, L - window), L)."""
     out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     hq, hkv = q.shape[1], k_cache.shape[1]
     rep = hq // hkv
@@ -259,6 +270,8 @@ def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale) -> 
         kk = kk.float().transpose(0, 1).repeat_interleave(rep, 0)   # [Hq, L, hd]
         vv = vv.float().transpose(0, 1).repeat_interleave(rep, 0)
         sc = (kk @ q[b].float().unsqueeze(-1)).squeeze(-1) * scale  # [Hq, L]
+        if 0 < window < L:
+            sc[:, : L - window] = float("-inf")
         out[b] = (sc.softmax(-1).unsqueeze(1) @ vv).squeeze(1).to(q.dtype)
     return out
 

@@ -552,7 +552,8 @@ def _dir_config(model_dir: str, name: str):
     from ..models.hf import config_from_hf, is_hf_dir
     d = Path(model_dir)
     if is_hf_dir(d):
-        return config_from_hf(json.loads((d / "config.json").read_text()), name)
+        return config_from_hf(json.loads((d / "config.json").read_text()), name,
+                              sliding_window=True)
     for c in [d / "config.json"] + sorted(d.glob("shard_*/config.json")):
         if c.exists():
             return ModelConfig.from_dict(json.loads(c.read_text()))

@@ -45,7 +45,7 @@ def export_shards(model_name: str, num_shards: int, output_dir: str = "model_sha
     if hf_dir is not None:
         from ..models.hf import config_from_hf
         cfg = config_from_hf(json.loads((Path(hf_dir) / "config.json").read_text()),
-                             model_name)
+                             model_name, sliding_window=True)
     cfg = cfg or get_config(model_name)
     plans = plan_stages(cfg, num_shards, policy)
     root = model_dir(output_dir, model_name)

@@ -5,8 +5,11 @@ cache write and attention in one launch), and the unfused plain / pipelined atte
 (timed apart from the separate RoPE + cache-write kernel). Times are per call from graph replays of 16 calls each; the KV
 bytes read per call give the achieved bandwidth, and the slope / intercept of time against
 context split the per-token (streaming) cost from the fixed (prologue, launch) cost.
+``--window W`` runs every kernel with a sliding window of W keys (0 = full attention): the
+bytes counted are then those of the min(ctx, W) keys a query sees. "auto" is the kernel and
+split count the engine would run.
 
-    python scripts/attn_probe.py [--batch 64,512] [--ctx 1,33,66,100,200,400]
+    python scripts/attn_probe.py [--batch 64,512] [--ctx 1,33,66,100,200,400] [--window W]
 """
 import argparse
 import json
@@ -23,15 +26,18 @@ def main():
     ap.add_argument("--batch", default="512")
     ap.add_argument("--ctx", default="1,33,66,100,200,400")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--window", type=int, default=0)
     a = ap.parse_args()
+    W = max(a.window, 0)
     from distributed_llm_inferencing_amd import ops
     dev = torch.device("cuda")
     hq, hkv, hd, bs = 32, 8, 128, 16
     R = 16
     N = (hq + 2 * hkv) * hd
     scale = hd ** -0.5
-    cos_sin = torch.randn(4096, hd, device=dev)
-    for B, ctx in [(int(b), int(c)) for b in a.batch.split(",") for c in a.ctx.split(",")]:
+    cases = [(int(b), int(c)) for b in a.batch.split(",") for c in a.ctx.split(",")]
+    cos_sin = torch.randn(max(4096, max(c for _, c in cases)), hd, device=dev)
+    for B, ctx in cases:
         nblk_seq = -(-ctx // bs)
         nblk = B * nblk_seq + 8
         kc = (torch.randn(nblk, hkv, bs, hd, device=dev) * 0.5).to(torch.bfloat16)
@@ -44,23 +50,24 @@ def main():
         slabs = (torch.randn(2, B, N, device=dev) * 0.02).to(torch.float16)
         qkv = (torch.randn(B, N, device=dev) * 0.5).to(torch.bfloat16)
         out = torch.empty(B, hq * hd, dtype=torch.bfloat16, device=dev)
-        kv_mb = B * hkv * ctx * 2 * hd * 2 / 1e6
+        kv_mb = B * hkv * ops.decode_span(ctx, W) * 2 * hd * 2 / 1e6
 
         def fused():
-            ops._native_call("dli_decode_attention_fused", ops._p(out), ops._p(slabs), 2,
+            ops._native_call("dli_decode_attention_fused_win", ops._p(out), ops._p(slabs), 2,
                              ops._p(pos), ops._p(slot), ops._p(cos_sin), ops._p(kc), ops._p(vc),
                              ops._p(bt), bt.stride(0), ops._p(cl), B, hq, hkv, hd, bs, scale, 1,
-                             ops._st())
+                             W, ops._st())
 
         def rope():
             ops.rope_and_cache(qkv, pos, slot, cos_sin, kc, vc, hq, hkv, hd)
 
         def attn():
-            ops.decode_attention(qkv, kc, vc, bt, cl, ctx, hq, hkv, hd, scale, out=out)
+            ops.decode_attention(qkv, kc, vc, bt, cl, ctx, hq, hkv, hd, scale, out=out,
+                                 window=W)
 
-        row = {"batch": B, "ctx": ctx, "kv_MB": round(kv_mb, 1)}
+        row = {"batch": B, "ctx": ctx, "window": W, "kv_MB": round(kv_mb, 1)}
         for name, fn, mode in (("fused", fused, None), ("rope", rope, None),
-                               ("plain", attn, 0), ("pipe", attn, 1)):
+                               ("plain", attn, 0), ("pipe", attn, 1), ("auto", attn, 2)):
             old = ops.decode_pipelined(mode) if mode is not None else None
             # R calls per graph: one replay's launch latency (~10-20 us of host time that the
             # events around a replay also measure) is spread over R kernels
