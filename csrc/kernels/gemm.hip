@@ -21,7 +21,8 @@
 // Epilogues: 0 bf16 store, 1 fp32 store (logits), 2 SiLU(gate)*up over the 16-row-interleaved
 // gate/up weight (output width N/2), 3 bias + tanh-GELU, 4 bias.
 //
-// Files: gemm_common.h (shared epilogue / split-K pieces), gemm_tiles.hip (ids 0-21, 23-25),
+// Files: gemm_common.h (shared epilogue / split-K pieces), gemm_tiles.hip (ids 0-21, 23-25,
+// 60-61: tiles 23 / 17 on the staggered two-group schedule),
 // gemm8p.hip (22, 26-28), gemm4w.h + gemm4w.hip (34, 41, 45), gemm4wp.hip (55: persistent
 // 45), gemv.hip (29-33 and the fused
 // batch-1 combine). The losing 4-wave A/B variants of round 4 are documented, not built
@@ -63,7 +64,8 @@ extern "C" int dli_gemm_grouped_gather(const void* A, int lda, const void* W, in
                                        const int* arow, const int* group_off, int groups,
                                        hipStream_t st) {
   if (M <= 0 || N <= 0) return 0;
-  const bool generic = (tile_cfg >= 0 && tile_cfg <= 21) || (tile_cfg >= 23 && tile_cfg <= 25);
+  const bool generic = (tile_cfg >= 0 && tile_cfg <= 21) || (tile_cfg >= 23 && tile_cfg <= 25) ||
+                       tile_cfg == 60 || tile_cfg == 61;
   if (!generic || arow == nullptr || group_off == nullptr || groups < 1 || K % BK || lda % 8 ||
       ldw % 8 || N % 32)
     return (int)hipErrorInvalidValue;

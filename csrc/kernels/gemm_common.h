@@ -196,6 +196,121 @@ __device__ __forceinline__ void store_silu_quad(void* C, int ldc, int row, int f
   }
 }
 
+// ---- 16-B epilogue stores for 2-byte outputs. A lane's packed quad of a 16-column block is
+// 8 B (uint2); lane (fr, fq) holds columns 4 fq .. 4 fq + 3 of its row, so a row receives a
+// block's 32 bytes from four lanes and the store tail issues one 8-B store per block. For two
+// ADJACENT blocks (j, j + 1), v_permlane16_swap_b32 vdst, src swaps the odd 16-lane rows of
+// vdst (lanes 16-31, 48-63) with the even rows of src (lanes 0-15, 32-47); with vdst = block
+// j's dword and src = block j + 1's dword, once per dword, the lanes then hold
+//   fq 0: block j   columns 0-7      fq 1: block j+1 columns 0-7
+//   fq 2: block j   columns 8-15     fq 3: block j+1 columns 8-15
+// i.e. 8 contiguous columns each: one 16-B store per lane replaces two 8-B stores (half the
+// store instructions at equal bytes, 64 contiguous bytes per row; the store tail is
+// issue-bound, cdna_hip_programming.md T21). The values are unchanged, only the lane that
+// stores them. The swap is a cross-lane operation: EVERY lane of the wave must execute it, so
+// the row / column predicates apply to the store alone. An odd block left over, rows or N
+// without 16-B alignment and the fp32 outputs keep the 8-B / per-column stores. So does the
+// SiLU*up epilogue: pairing two gate/up results into one 16-B store ran the M = 512 gate/up
+// GEMM on the 256x256 8-phase tile 2.9 % slower (profiles/r7/README.md).
+__device__ __forceinline__ uint4 widen_pair(uint2 a, uint2 b) {
+  const auto x = __builtin_amdgcn_permlane16_swap(a.x, b.x, false, false);
+  const auto y = __builtin_amdgcn_permlane16_swap(a.y, b.y, false, false);
+  return uint4{x[0], y[0], x[1], y[1]};
+}
+// first of the lane's 8 columns after widen_pair, relative to block j's first column
+__device__ __forceinline__ int wide_col(int fq) { return 16 * (fq & 1) + 8 * (fq >> 1); }
+
+// 16-B stores need every row start and 8-column run aligned
+__device__ __forceinline__ bool slab_wide(int N, const float* ws) {
+  return (N & 7) == 0 && ((uintptr_t)ws & 15) == 0;
+}
+template <int EPI>
+__device__ __forceinline__ bool out_wide(const void* C, int ldc, int N, const u16* bias) {
+  if (EPI == EPI_F32 || EPI == EPI_SLAB16 || EPI == EPI_SILU) return false;
+  return ((N | ldc) & 7) == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)bias & 7) == 0;
+}
+
+// one lane's row of NB adjacent 16-column blocks of the fp16 slab image: p = &slab[row][first
+// column of block 0] (fp32-indexed, as slab_quad16), left = N - that column, ok = row in range
+template <int NB>
+__device__ __forceinline__ void slab_row16(float* p, const f32x4 (&v)[NB], bool ok, int left,
+                                           const float* ws, bool vec, bool wide, int fq) {
+  if (wide) {
+    u16* q = (u16*)ws + (p - ws);
+#pragma unroll
+    for (int j = 0; j + 1 < NB; j += 2) {
+      uint2 a, b;
+      a.x = pack2h(v[j][0] * SLAB16_SCALE, v[j][1] * SLAB16_SCALE);
+      a.y = pack2h(v[j][2] * SLAB16_SCALE, v[j][3] * SLAB16_SCALE);
+      b.x = pack2h(v[j + 1][0] * SLAB16_SCALE, v[j + 1][1] * SLAB16_SCALE);
+      b.y = pack2h(v[j + 1][2] * SLAB16_SCALE, v[j + 1][3] * SLAB16_SCALE);
+      const uint4 w = widen_pair(a, b);
+      const int c = 16 * j + wide_col(fq);
+      if (ok && c < left) *reinterpret_cast<uint4*>(q + c) = w;
+    }
+    if (NB & 1) {
+      const int c = 16 * (NB - 1) + 4 * fq;
+      if (ok && c < left) slab_quad16(p + c, v[NB - 1], vec, left - c, ws);
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int c = 16 * j + 4 * fq;
+    if (ok && c < left) slab_quad16(p + c, v[j], vec, left - c, ws);
+  }
+}
+
+// the packed bf16 quad of store_quad's vector path (bias / GELU applied); inb: the quad's
+// columns exist (the bias is not read past N)
+template <int EPI>
+__device__ __forceinline__ uint2 pack_quad(f32x4 v, const u16* bias, int col, bool inb) {
+  float o[4] = {v[0], v[1], v[2], v[3]};
+  if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
+    uint2 b = uint2{0u, 0u};
+    if (inb) b = *reinterpret_cast<const uint2*>(bias + col);
+    o[0] += __uint_as_float(b.x << 16); o[1] += __uint_as_float(b.x & 0xffff0000u);
+    o[2] += __uint_as_float(b.y << 16); o[3] += __uint_as_float(b.y & 0xffff0000u);
+  }
+  if (EPI == EPI_BIAS_GELU) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = gelu_f(o[r]);
+  }
+  uint2 pk;
+  pk.x = pack2bf(o[0], o[1]);
+  pk.y = pack2bf(o[2], o[3]);
+  return pk;
+}
+
+// one lane's row of NB adjacent 16-column blocks of the output: col0 = first column of block 0
+template <int EPI, int NB>
+__device__ __forceinline__ void store_row(void* C, int ldc, int row, int col0, int N,
+                                          const f32x4 (&v)[NB], const u16* bias, bool ok,
+                                          bool vec, bool wide, int fq) {
+  if (wide) {
+    u16* prow = (u16*)C + (long)row * ldc;
+#pragma unroll
+    for (int j = 0; j + 1 < NB; j += 2) {
+      const int ca = col0 + 16 * j + 4 * fq;
+      const uint2 a = pack_quad<EPI>(v[j], bias, ca, ca < N);
+      const uint2 b = pack_quad<EPI>(v[j + 1], bias, ca + 16, ca + 16 < N);
+      const uint4 w = widen_pair(a, b);
+      const int c = col0 + 16 * j + wide_col(fq);
+      if (ok && c < N) *reinterpret_cast<uint4*>(prow + c) = w;
+    }
+    if (NB & 1) {
+      const int c = col0 + 16 * (NB - 1) + 4 * fq;
+      if (ok && c < N) store_quad<EPI>(C, ldc, row, c, N, v[NB - 1], bias, vec);
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int c = col0 + 16 * j + 4 * fq;
+    if (ok && c < N) store_quad<EPI>(C, ldc, row, c, N, v[j], bias, vec);
+  }
+}
+
 // s_waitcnt vmcnt(N) with expcnt/lgkmcnt left at their maxima (gfx9 encoding)
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

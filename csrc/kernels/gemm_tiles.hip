@@ -1,9 +1,9 @@
-// Generic LDS-tiled MFMA GEMM family (tile ids 0-21, 23-25): WM x WN waves, BM x BN x 64
+// Generic LDS-tiled MFMA GEMM family (tile ids 0-21, 23-25, 60-61): WM x WN waves, BM x BN x 64
 // block tiles, 2 or 3 LDS stages filled by LDS-DMA. Split-K writes fp32 slabs for the fused
 // consumers (fused_reduce.hip) or reduces them with splitk_reduce_kernel.
 #include "gemm_common.h"
 
-template <int BM, int BN, int EPI, int NS, int WM, int WN>
+template <int BM, int BN, int EPI, int NS, int WM, int WN, int STAG = 0>
 __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     const u16* __restrict__ A, int lda, const u16* __restrict__ W, int ldw,
     void* __restrict__ C, int ldc, int M, int N, int K, int k_split_len,
@@ -116,7 +116,100 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     }
   };
 
-  if (NS == 2) {
+  if constexpr (STAG != 0) {
+    // Staggered two-group schedule for the 2 x 4-wave, 3-stage tiles (MI355X_MICROARCH.md
+    // 'Two waves per SIMD' item 9; the stagger of gemm8p_kernel). The lockstep loop below
+    // sends all eight waves into their ds_read burst, their MFMAs and the barrier together,
+    // so no MFMA issues under the reads. Here group g = wid >> 2 (= wm, the wave's 64-row
+    // half; waves w and w + 4 share a SIMD) splits every K-step into a LOAD and a MATRIX
+    // segment closed by raw s_barriers, and group 1 runs one segment behind group 0: on
+    // every SIMD one wave is in MATRIX while its partner is in LOAD.
+    //
+    //   segment s | group 0                  | group 1
+    //   2T        | LOAD(T)                  | MATRIX(T-1)
+    //   2T + 1    | MATRIX(T)                | LOAD(T)
+    //
+    //   LOAD(T):   ds_read_b128 of every fragment of K-tile T (both kk halves) from buffer
+    //              T % 3; the wave's share of the LDS-DMA of K-tile T+2 into buffer
+    //              (T+2) % 3; vmcnt(INSTR) (K-tile T+1 retired, T+2 stays in flight; vmcnt(0)
+    //              in the tail, where nothing was issued); lgkmcnt(0); barrier
+    //   MATRIX(T): the K-tile's MI x NI x 2 MFMAs (kk 0 then 1: the lockstep order per
+    //              accumulator, so the results are bit-identical); barrier
+    //
+    //   buffer (T+2) % 3 = (T-1) % 3: last ds_read in LOAD(T-1) = segments 2T-2 (group 0) and
+    //     2T-1 (group 1), each with lgkmcnt(0) before its closing barrier; restaged in
+    //     segments 2T (group 0) and 2T+1 (group 1): one segment after the last read (WAR).
+    //   K-tile T+1: issued in LOAD(T-1) (or the prologue), retired by group 0's vmcnt in
+    //     segment 2T and by group 1's in segment 2T+1, each before the segment's closing
+    //     barrier; first read in segment 2T+2 (group 0), after the barrier that closes 2T+1 —
+    //     one barrier more than one group alone would need (RAW).
+    //   prologue: K-tiles 0 and 1 issued, vmcnt(INSTR) retires K-tile 0 (vmcnt(0) if nk = 1),
+    //     barrier; group 1 then waits one more barrier (segment 0), group 0 one after the
+    //     loop, so every wave passes 2 nk + 2 barriers.
+    static_assert(WM == 2 && WN == 4 && NS == 3, "staggered schedule: 2 x 4 waves, 3 stages");
+    constexpr int INSTR = A_INSTR + W_INSTR;
+    const int g = __builtin_amdgcn_readfirstlane(wid) >> 2;
+    auto barrier = [&]() {
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" ::: "memory");
+    };
+    if (nk > 0) stage(0, 0);
+    if (nk > 1) { stage(1, 1); wait_vmcnt<INSTR>(); }
+    else wait_vmcnt<0>();
+    barrier();
+    if (g == 1) {                                    // stagger: group 1 runs one segment behind
+      barrier();
+      __builtin_amdgcn_s_setprio(1);                 // static priority for the younger half
+    }
+    int cur = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+      // ---- LOAD
+      const char* abuf = smem + cur * BUF;
+      const char* wbuf = abuf + A_BYTES;
+      bf16x8 af[2][MI], bfr[2][NI];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int c = kk * 4 + fq;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          const int r = a_row[i];
+          af[kk][i] =
+              *reinterpret_cast<const bf16x8*>(abuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+        }
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+          const int r = w_row[j];
+          bfr[kk][j] =
+              *reinterpret_cast<const bf16x8*>(wbuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+        }
+      }
+      if (kt + 2 < nk) {
+        int nb = cur + 2;
+        if (nb >= NS) nb -= NS;
+        stage(nb, kt + 2);
+        wait_vmcnt<INSTR>();
+      } else {
+        wait_vmcnt<0>();
+      }
+      __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): this segment's reads done
+      barrier();
+      // ---- MATRIX
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int j = 0; j < NI; ++j)
+            acc[i][j] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[kk][j], af[kk][i], acc[i][j], 0, 0, 0);
+      barrier();
+      cur = (cur + 1 == NS) ? 0 : cur + 1;
+    }
+    if (g == 0) barrier();                           // balance group 1's stagger barrier
+  } else if (NS == 2) {
     // 2 LDS buffers: the next tile's DMA overlaps this tile's MFMAs; drained every K-step
     if (nk > 0) stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -164,6 +257,17 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     float* slab = ws + (long)ks * M * N;
     const int sm = g_slab_store;
     const bool vec = (N & 3) == 0;
+    const int col0 = n0 + wn * TN;
+    if (EPI == EPI_SLAB16) {
+      const bool wide = slab_wide(N, ws);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int row = m0 + wm * TM + 16 * i + fr;
+        slab_row16<NI>(slab + (long)(row0 + row) * N + col0, acc[i], row < Mg, N - col0, ws, vec,
+                       wide, fq);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       const int row = m0 + wm * TM + 16 * i + fr;
@@ -171,15 +275,15 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
       float* srow = slab + (long)(row0 + row) * N;
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
-        const int col = n0 + wn * TN + 16 * j + 4 * fq;
+        const int col = col0 + 16 * j + 4 * fq;
         if (col >= N) continue;
-        if (EPI == EPI_SLAB16) slab_quad16(srow + col, acc[i][j], vec, N - col, ws);
-        else slab_quad(srow + col, acc[i][j], sm, vec, N - col, ws);
+        slab_quad(srow + col, acc[i][j], sm, vec, N - col, ws);
       }
     }
     return;
   }
   const bool vec = out_vec<EPI>(C, ldc, N, bias);
+  const bool wide = out_wide<EPI>(C, ldc, N, bias);
   if (EPI == EPI_SILU) {
     // column blocks j (even) = gate, j+1 = up of the same 16 features
 #pragma unroll
@@ -199,16 +303,12 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     const int row = m0 + wm * TM + 16 * i + fr;
-    if (row >= Mg) continue;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int col = n0 + wn * TN + 16 * j + 4 * fq;
-      if (col < N) store_quad<EPI>(C, ldc, row0 + row, col, N, acc[i][j], bias, vec);
-    }
+    store_row<EPI, NI>(C, ldc, row0 + row, n0 + wn * TN, N, acc[i], bias, row < Mg, vec, wide,
+                       fq);
   }
 }
 
-template <int BM, int BN, int EPI, int NS, int WM = 2, int WN = 2>
+template <int BM, int BN, int EPI, int NS, int WM = 2, int WN = 2, int STAG = 0>
 static int launch_cfg(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
                       int N, int K, int splits, const void* bias, void* ws,
                       const int* group_off, int groups, hipStream_t st) {
@@ -220,12 +320,12 @@ static int launch_cfg(const void* A, int lda, const void* W, int ldw, void* C, i
   const size_t lds = NS * (size_t)(BM + BN) * BK * 2;
   static bool attr_done = false;                   // > 64 KiB dynamic LDS needs the opt-in
   if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN>,
+    hipFuncSetAttribute((const void*)gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG>,
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
   dim3 grid(tiles, splits, groups);
-  gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN><<<grid, 64 * WM * WN, lds, st>>>(
+  gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG><<<grid, 64 * WM * WN, lds, st>>>(
       (const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K, ksl, (const u16*)bias,
       (float*)ws, group_off);
   if (splits > 1 && C != nullptr) {       // C == nullptr: leave the fp32 partial slabs for a
@@ -257,6 +357,9 @@ static int dispatch_tiles(int tile_cfg, DLI_GEMM_ARGS) {
     // 192-wide tiles: N = 6144 (fused QKV) = 32 column tiles, so M = 512 fills 256 CUs with
     // 4 x 32 x split 2 (128-row) or 2 x 32 x split 4 (256-row) workgroups of 8 waves
     DLI_CFG8(23, 128, 192, 3, 2, 4) DLI_CFG8(24, 128, 192, 2, 2, 4) DLI_CFG8(25, 256, 192, 2, 4, 2)
+    // tiles 23 / 17 on the staggered two-group schedule (STAG): same tile, ring and bits
+    case 60: return launch_cfg<128, 192, EPI, 3, 2, 4, 1>(DLI_GEMM_PASS);
+    case 61: return launch_cfg<128, 256, EPI, 3, 2, 4, 1>(DLI_GEMM_PASS);
 #undef DLI_CFG8
 #undef DLI_CFG
     default: return DLI_NOT_MINE;
