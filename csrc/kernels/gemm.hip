@@ -21,12 +21,12 @@
 // Epilogues: 0 bf16 store, 1 fp32 store (logits), 2 SiLU(gate)*up over the 16-row-interleaved
 // gate/up weight (output width N/2), 3 bias + tanh-GELU, 4 bias.
 //
-// Files: gemm_common.h (shared epilogue / split-K pieces), gemm_tiles.hip (ids 0-21, 23-25,
-// 60-61: tiles 23 / 17 on the staggered two-group schedule),
-// gemm8p.hip (22, 26-28), gemm4w.h + gemm4w.hip (34, 41, 45), gemm4wp.hip (55: persistent
-// 45), gemv.hip (29-33 and the fused
-// batch-1 combine). The losing 4-wave A/B variants of round 4 are documented, not built
-// (profiles/r4/gemm4w/).
+// Files: gemm_common.h (what the families share: block coordinates, epilogue, launcher,
+// split-K pieces), gemm_tiles.hip (the generic tiles), gemm8p.hip (8-phase ping-pong),
+// gemm4w.h + gemm4w.hip (4 waves) and gemm4wp.hip (their persistent form), gemv.hip (the
+// M <= 4 weight stream and the fused batch-1 combine). Which tile id is which kernel, tile
+// size and wave layout: the one table, TILE_TABLE in ops/gemm.py; each family's dispatch
+// switch is its C++ side.
 #include "gemm_common.h"
 
 extern "C" int dli_gemm_set_slab_store(int mode) {
@@ -47,15 +47,6 @@ extern "C" int dli_gemm_set_slab_store_family(int family, int mode) {
   }
 }
 
-// tile_cfg: 0=64x64 1=64x128 2=128x128 3=128x256 4=256x128 (2 LDS stages); 5..9 = the same
-// tiles with 3 LDS stages (one tile in flight across the barrier); 10/11 = 192x128 with 2/3
-// stages, 12 = 160x128 (MoE experts of ~130-190 rows in one pass); 13-17 = 8-wave tiles
-// 256x256, 256x128, 128x256 (2 stages) and 256x128, 128x256 (3 stages); 18/19 = 128x96 and
-// 20/21 = 128x64 with 2/3 stages; 22 = 256x256 8-phase ping-pong; 23/24 = 128x192 (3/2
-// stages), 25 = 256x192, 8 waves; 26 = 256x224 ping-pong; 29-33 = the M <= 4 weight
-// stream (16 / 32 rows per workgroup, dispatch_gemv); 55 = tile 45 persistent (one workgroup
-// per CU walks its tiles, no split-K / grouped mode). ws: fp32 [splits, M, N] when splits>1.
-// group_off (nullable): int[groups+1] row offsets; M is then the max rows of any group.
 // Grouped SiLU*up GEMM whose permuted row p reads activation row arow[p] (the MoE gate/up
 // projection without the gathered copy of its input rows): the generic tile family only,
 // unsplit. M: the row bound per group, as dli_gemm's grouped mode.
@@ -64,18 +55,20 @@ extern "C" int dli_gemm_grouped_gather(const void* A, int lda, const void* W, in
                                        const int* arow, const int* group_off, int groups,
                                        hipStream_t st) {
   if (M <= 0 || N <= 0) return 0;
-  const bool generic = (tile_cfg >= 0 && tile_cfg <= 21) || (tile_cfg >= 23 && tile_cfg <= 25) ||
-                       tile_cfg == 60 || tile_cfg == 61;
-  if (!generic || arow == nullptr || group_off == nullptr || groups < 1 || K % BK || lda % 8 ||
+  if (arow == nullptr || group_off == nullptr || groups < 1 || K % BK || lda % 8 ||
       ldw % 8 || N % 32)
     return (int)hipErrorInvalidValue;
   const void* bias = arow;
   void* ws = nullptr;
   const int* go = group_off;
   const int splits = 1;
-  return gemm_tiles_dispatch(EPI_SILU, tile_cfg, DLI_GEMM_PASS);
+  const int r = gemm_tiles_dispatch(EPI_SILU, tile_cfg, DLI_GEMM_PASS);
+  return r == DLI_NOT_MINE ? (int)hipErrorInvalidValue : r;
 }
 
+// tile_cfg: a tile id of ops/gemm.py's TILE_TABLE (or a GEMV_TILES id, gemv.hip). ws: fp32
+// [splits, M, N] when splits > 1. group_off (nullable): int[groups+1] row offsets; M is then
+// the max rows of any group.
 extern "C" int dli_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
                         int N, int K, int epi, int tile_cfg, int splits, const void* bias,
                         void* ws, const int* group_off, int groups, hipStream_t st) {

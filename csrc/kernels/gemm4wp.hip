@@ -1,5 +1,5 @@
 // Persistent form of the 4-wave two-barrier 256x256 GEMM (tile 55; tile 45 = gemm4w_kernel
-// <EPI, 8 | 4096> is its one-tile-per-workgroup form). VERDICT r4 item 4: the prefill
+// <EPI, false, true> is its one-tile-per-workgroup form). VERDICT r4 item 4: the prefill
 // projections pay, per 256x256 tile, a prologue (the first two K-tiles' LDS-DMA latency with
 // the matrix pipe idle) and an epilogue (the 128-256 KB store tail) that a workgroup-per-tile
 // grid cannot hide. Here one workgroup per CU walks tiles v = blockIdx.x, + gridDim.x, ...
@@ -33,13 +33,7 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
 
   // virtual tile id -> (m0, n0): tile 45's XCD remap + GM-4 grouped order
   auto coords = [&](int v, int& m0, int& n0) {
-    const int tile = xcd_remap(v, nwg);
-    const int per_group = GM * tiles_n;
-    const int first_m = (tile / per_group) * GM;
-    const int gsz = min(tiles_m - first_m, GM);
-    const int in_g = tile % per_group;
-    m0 = (first_m + in_g % gsz) * BM;
-    n0 = (in_g / gsz) * BN;
+    tile_origin<BM, BN, GM>(xcd_remap(v, nwg), tiles_m, tiles_n, m0, n0);
   };
 
   // ---- staging: piece f (0..15) of K-tile kg of the tile whose operand panels start at
@@ -67,35 +61,22 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
   };
 
   const int fr = lane & 15, fq = lane >> 4;
-  auto read_frag = [&](const char* part, int row, int kk) -> bf16x8 {
-    const int c = kk * 4 + fq;
-    return *reinterpret_cast<const bf16x8*>(part + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-  };
   const int arow = wm * 128 + fr, wrow = wn * 128 + fr;
   auto abuf = [&](int kt) -> const char* { return smem + (kt & 1) * BUF; };
   auto wbuf = [&](int kt) -> const char* { return smem + (kt & 1) * BUF + A_BYTES; };
 
-  auto barrier = [&]() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-  };
-
   f32x4 acc[8][8];
   bf16x8 a0[8], b0[8], a1[8], b1[8];
   auto read_f0 = [&](int kt) {       // kk = 0 fragments of K-tile kt (order A0, B0..B7, A1..)
-    a0[0] = read_frag(abuf(kt), arow, 0);
+    a0[0] = read_frag(abuf(kt), arow, 0, fq);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) b0[j] = read_frag(wbuf(kt), wrow + 16 * j, 0);
+    for (int j = 0; j < 8; ++j) b0[j] = read_frag(wbuf(kt), wrow + 16 * j, 0, fq);
 #pragma unroll
-    for (int i = 1; i < 8; ++i) a0[i] = read_frag(abuf(kt), arow + 16 * i, 0);
+    for (int i = 1; i < 8; ++i) a0[i] = read_frag(abuf(kt), arow + 16 * i, 0, fq);
   };
   auto read_fx = [&](int f, bf16x8 (&av)[8], bf16x8 (&bv)[8], const char* pa, const char* pw,
                      int kk) __attribute__((always_inline)) {
-    if (f >= 1 && f <= 8) bv[f - 1] = read_frag(pw, wrow + 16 * (f - 1), kk);
-    else { const int ia = f == 0 ? 0 : f - 8; av[ia] = read_frag(pa, arow + 16 * ia, kk); }
+    read_frag_4w(f, av, bv, pa, pw, arow, wrow, kk, fq);
   };
 
   // one K-tile of the two-barrier schedule (gemm4w.h ktile2): MFMAs 0-15 read F1(kt), B1
@@ -116,8 +97,8 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
         __builtin_amdgcn_sched_barrier(0);
       }
       if (q == QB1) {
-        __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0)
-        barrier();
+        lgkmcnt0();
+        raw_barrier();
       }
       if (stg && q > QB1 && q <= QB1 + 80 && (q - QB1 - 1) % 5 == 0) {
         stage_piece(kg, kt & 1, (q - QB1 - 1) / 5);
@@ -125,7 +106,7 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
       }
       if (q == QB2 && more) {
         wait_vmcnt<stg ? 16 : 0>();
-        barrier();
+        raw_barrier();
       }
       if (more && q > QB2 && q <= QB2 + 16) {
         read_fx(q - QB2 - 1, a0, b0, nab, nwb, 0);
@@ -149,14 +130,7 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
         step(64 + 8 * u + v);
       }
   };
-  auto vget = [&](const f32x4& a) -> f32x4 {
-    f32x4 v;
-    asm volatile("" : "=v"(v) : "0"(a));
-    return v;
-  };
-
   using T_ = std::integral_constant<bool, true>;
-  using F_ = std::integral_constant<bool, false>;
   int v = blockIdx.x;
   if (v >= nwg) return;                              // wave-uniform: every wave exits
   int m0, n0;
@@ -169,7 +143,7 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
 #pragma unroll
   for (int f = 0; f < 16; ++f) stage_piece(1, 1, f);
   wait_vmcnt<16>();
-  barrier();
+  raw_barrier();
 
   while (true) {                                     // every wave runs the same tiles
     const int vn = v + (int)gridDim.x;
@@ -206,36 +180,12 @@ __global__ void __launch_bounds__(256, 1) gemm4wp_kernel(
     // ---- epilogue of tile (m0, n0), transposed accumulators:
     // acc[I][J][r] = C[m0 + 128 wm + 16I + fr][n0 + 128 wn + 16J + 4fq + r]
     const int wr0 = m0 + 128 * wm, wc0 = n0 + 128 * wn;
-    const bool vec = out_vec<EPI>(C, ldc, N, bias);
-    if (EPI == EPI_SILU) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int row = wr0 + 16 * i + fr;
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          const f32x4 g = vget(acc[i][j]), u = vget(acc[i][j + 1]);
-          const int gcol = wc0 + 16 * j;
-          if (row < M && gcol < N)
-            store_silu_quad(C, ldc, row, (gcol >> 5) * 16 + 4 * fq, g, u, vec);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int row = wr0 + 16 * i + fr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const f32x4 val = vget(acc[i][j]);
-          const int col = wc0 + 16 * j + 4 * fq;
-          if (row < M && col < N) store_quad<EPI>(C, ldc, row, col, N, val, bias, vec);
-        }
-      }
-    }
+    store_out_4w<EPI>(acc, wr0, wc0, 0, M, C, ldc, N, bias, fr, fq);
     // the next tile's K-tiles 0 and 1 (issued in the last two K-tiles) landed for every wave
     // (also before exiting: no LDS-DMA outlives the workgroup)
     wait_vmcnt<0>();
     if (!has_next) break;
-    barrier();
+    raw_barrier();
     v = vn;
     m0 = mn;
     n0 = nn;
@@ -256,8 +206,9 @@ static int launch_4wp(const void* A, int lda, const void* W, int ldw, void* C, i
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (cus <= 0) cus = 256;
-    hipFuncSetAttribute((const void*)gemm4wp_kernel<EPI>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute((const void*)gemm4wp_kernel<EPI>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { cus = 0; return (int)e; }
   }
   const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
   // one workgroup per CU (128 KiB of LDS each); a multiple of 8 keeps every workgroup's

@@ -1,6 +1,7 @@
 // Shared pieces of the bf16 MFMA GEMM families (gemm_tiles.hip, gemm8p.hip, gemm4w.hip,
 // gemv.hip; dispatched by gemm.hip's dli_gemm): epilogue stores, split-K slab stores, the
-// counted-vmcnt helpers, the split-K tile mapping and the split-K reduce kernel.
+// waitcnt / barrier / fragment helpers, the block -> tile mapping, the shared epilogue, the
+// split-K reduce kernel and the launcher.
 // Every kernel computes C[M,N] = A[M,K] . W[N,K]^T with the W fragment as MFMA operand A
 // (transposed accumulators, see below). Static / inline only: each family is its own
 // translation unit.
@@ -138,6 +139,27 @@ __device__ __forceinline__ void slab_quad(float* p, f32x4 v, int mode, bool vec,
   slab_quad_fp32(p, v, mode, vec, left);
 }
 
+// a quad packed to bf16 with the bias / GELU of the epilogue applied; inb: the quad's columns
+// exist (the bias is not read past N)
+template <int EPI>
+__device__ __forceinline__ uint2 pack_quad(f32x4 v, const u16* bias, int col, bool inb) {
+  float o[4] = {v[0], v[1], v[2], v[3]};
+  if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
+    uint2 b = uint2{0u, 0u};
+    if (inb) b = *reinterpret_cast<const uint2*>(bias + col);
+    o[0] += __uint_as_float(b.x << 16); o[1] += __uint_as_float(b.x & 0xffff0000u);
+    o[2] += __uint_as_float(b.y << 16); o[3] += __uint_as_float(b.y & 0xffff0000u);
+  }
+  if (EPI == EPI_BIAS_GELU) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = gelu_f(o[r]);
+  }
+  uint2 pk;
+  pk.x = pack2bf(o[0], o[1]);
+  pk.y = pack2bf(o[2], o[3]);
+  return pk;
+}
+
 // four consecutive output columns [col, col + 4) of one row; vec = (N % 4 == 0 && ldc % 4
 // == 0): one 16-B (fp32) / 8-B (bf16) store, else per-column stores for the row's tail
 template <int EPI>
@@ -153,20 +175,7 @@ __device__ __forceinline__ void store_quad(void* C, int ldc, int row, int col, i
     *reinterpret_cast<f32x4*>((float*)C + (long)row * ldc + col) = v;
     return;
   }
-  float o[4] = {v[0], v[1], v[2], v[3]};
-  if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
-    const uint2 b = *reinterpret_cast<const uint2*>(bias + col);
-    o[0] += __uint_as_float(b.x << 16); o[1] += __uint_as_float(b.x & 0xffff0000u);
-    o[2] += __uint_as_float(b.y << 16); o[3] += __uint_as_float(b.y & 0xffff0000u);
-  }
-  if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[r] = gelu_f(o[r]);
-  }
-  uint2 pk;
-  pk.x = pack2bf(o[0], o[1]);
-  pk.y = pack2bf(o[2], o[3]);
-  *reinterpret_cast<uint2*>((u16*)C + (long)row * ldc + col) = pk;
+  *reinterpret_cast<uint2*>((u16*)C + (long)row * ldc + col) = pack_quad<EPI>(v, bias, col, true);
 }
 
 // the vector epilogue needs every row start and column quad aligned: N and ldc multiples
@@ -261,27 +270,6 @@ __device__ __forceinline__ void slab_row16(float* p, const f32x4 (&v)[NB], bool 
   }
 }
 
-// the packed bf16 quad of store_quad's vector path (bias / GELU applied); inb: the quad's
-// columns exist (the bias is not read past N)
-template <int EPI>
-__device__ __forceinline__ uint2 pack_quad(f32x4 v, const u16* bias, int col, bool inb) {
-  float o[4] = {v[0], v[1], v[2], v[3]};
-  if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
-    uint2 b = uint2{0u, 0u};
-    if (inb) b = *reinterpret_cast<const uint2*>(bias + col);
-    o[0] += __uint_as_float(b.x << 16); o[1] += __uint_as_float(b.x & 0xffff0000u);
-    o[2] += __uint_as_float(b.y << 16); o[3] += __uint_as_float(b.y & 0xffff0000u);
-  }
-  if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[r] = gelu_f(o[r]);
-  }
-  uint2 pk;
-  pk.x = pack2bf(o[0], o[1]);
-  pk.y = pack2bf(o[2], o[3]);
-  return pk;
-}
-
 // one lane's row of NB adjacent 16-column blocks of the output: col0 = first column of block 0
 template <int EPI, int NB>
 __device__ __forceinline__ void store_row(void* C, int ldc, int row, int col0, int N,
@@ -330,6 +318,26 @@ __device__ __forceinline__ void wait_ahead(int ahead) {
   wait_vmcnt<0>();
 }
 
+// s_waitcnt lgkmcnt(0) with vmcnt / expcnt left at their maxima: the wave's ds_reads done
+__device__ __forceinline__ void lgkmcnt0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
+// a raw s_barrier (a __syncthreads() would emit vmcnt(0) and drain the LDS-DMA in flight)
+// that neither the compiler's memory operations nor its scheduler move across
+__device__ __forceinline__ void raw_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+
+// one MFMA operand fragment (8 bf16 of K half kk, K quarter fq = lane / 16) of tile row `row`
+// from an LDS part of 128-B rows whose 16-B chunk c is stored at chunk c ^ ((row >> 1) & 7)
+__device__ __forceinline__ bf16x8 read_frag(const char* part, int row, int kk, int fq) {
+  const int c = kk * 4 + fq;
+  return *reinterpret_cast<const bf16x8*>(part + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
+}
+
 // Block -> (output tile, K split). Without split-K: the XCD remap over tiles (n-major order,
 // so an XCD's tiles share W panels). With split-K, (split, tile) is one split-major index
 // remapped over the whole grid, so an XCD's blocks work on ONE K slice: its L2 fetches that
@@ -346,6 +354,120 @@ __device__ __forceinline__ void split_tile(int nwg, bool grouped, int& tile, int
   const int lg = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), total);
   ks = lg / nwg;
   tile = lg - ks * nwg;
+}
+
+// tile index -> tile origin. GM = 1: n-major order (consecutive tiles share one W panel).
+// GM > 1: grouped order, an XCD's ~32 consecutive tiles cover GM tile-rows x 32/GM
+// tile-columns, so its CUs share both A and W panels in its L2
+template <int BM, int BN, int GM>
+__device__ __forceinline__ void tile_origin(int tile, int tiles_m, int tiles_n, int& m0, int& n0) {
+  if (GM > 1) {
+    const int per_group = GM * tiles_n;
+    const int first_m = (tile / per_group) * GM;
+    const int gsz = min(tiles_m - first_m, GM);
+    const int in_g = tile % per_group;
+    m0 = (first_m + in_g % gsz) * BM;
+    n0 = (in_g / gsz) * BN;
+  } else {
+    m0 = (tile % tiles_m) * BM;
+    n0 = (tile / tiles_m) * BN;
+  }
+}
+
+// What a workgroup works on: rows [row0 + m0, ..) of A / C within a group of Mg rows (grouped
+// mode: grid.z = group, rows [off[g], off[g+1]), weights W + g N ldw; else the whole matrix,
+// M = max rows of any group), columns from n0, K-tiles [kb / BK, kb / BK + nk) of split ks.
+// A block with m0 >= Mg has nothing to do (block-uniform).
+struct BlockCoord {
+  int row0, Mg, m0, n0, kb, nk, ks;
+  const u16* Wg;
+};
+template <int BM, int BN, int GM>
+__device__ __forceinline__ BlockCoord block_coord(const u16* W, int ldw, int M, int N, int K,
+                                                  int k_split_len, const int* group_off) {
+  BlockCoord b;
+  b.row0 = 0;
+  b.Mg = M;
+  b.Wg = W;
+  if (group_off != nullptr) {
+    b.row0 = group_off[blockIdx.z];
+    b.Mg = group_off[blockIdx.z + 1] - b.row0;
+    b.Wg = W + (long)blockIdx.z * N * ldw;
+  }
+  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+  int tile;
+  split_tile(tiles_m * tiles_n, group_off != nullptr, tile, b.ks);
+  tile_origin<BM, BN, GM>(tile, tiles_m, tiles_n, b.m0, b.n0);
+  b.kb = b.ks * k_split_len;
+  b.nk = min(k_split_len, K - b.kb) / BK;
+  return b;
+}
+
+// The epilogue of a wave holding MI x NI transposed accumulator blocks:
+// acc[i][j][r] = C[wr0 + 16 i + fr][wc0 + 16 j + 4 fq + r] (wr0 within the group's rows).
+// Split-K (grid.y > 1): the fp32 slab of split b.ks, or its fp16 image (EPI_SLAB16). Else the
+// fused store: SiLU(gate) * up over the block pairs (j, j + 1), j even, or a row of blocks with
+// bias / GELU. With NI odd the wave's pairs are not (even, odd) blocks: such a kernel stores
+// its SiLU result itself (gemm8p224_kernel) and nothing is stored here. Used by the 8-phase
+// kernels. gemm_bf16_kernel keeps the same text inline (hipcc allocated its registers
+// differently through this function) and the 4-wave kernels an epilogue of their own (pinned
+// accumulator copies, gemm4w.h).
+template <int EPI, int MI, int NI>
+__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[MI][NI], int wr0, int wc0,
+                                              const BlockCoord& b, void* C, int ldc, int M, int N,
+                                              const u16* bias, float* ws, int fr, int fq) {
+  if (gridDim.y > 1) {
+    float* slab = ws + (long)b.ks * M * N;
+    const int sm = g_slab_store;
+    const bool vec = (N & 3) == 0;
+    if (EPI == EPI_SLAB16) {
+      const bool wide = slab_wide(N, ws);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int row = wr0 + 16 * i + fr;
+        slab_row16<NI>(slab + (long)(b.row0 + row) * N + wc0, acc[i], row < b.Mg, N - wc0, ws,
+                       vec, wide, fq);
+      }
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int row = wr0 + 16 * i + fr;
+      if (row >= b.Mg) continue;
+      float* srow = slab + (long)(b.row0 + row) * N;
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const int col = wc0 + 16 * j + 4 * fq;
+        if (col >= N) continue;
+        slab_quad(srow + col, acc[i][j], sm, vec, N - col, ws);
+      }
+    }
+    return;
+  }
+  const bool vec = out_vec<EPI>(C, ldc, N, bias);
+  const bool wide = out_wide<EPI>(C, ldc, N, bias);
+  if constexpr (EPI == EPI_SILU) {
+    if constexpr (NI % 2 == 0) {
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int row = wr0 + 16 * i + fr;
+        if (row >= b.Mg) continue;
+#pragma unroll
+        for (int j = 0; j < NI; j += 2) {
+          const int gcol = wc0 + 16 * j;             // first gate column of the pair
+          if (gcol < N)
+            store_silu_quad(C, ldc, b.row0 + row, (gcol >> 5) * 16 + 4 * fq, acc[i][j],
+                            acc[i][j + 1], vec);
+        }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int row = wr0 + 16 * i + fr;
+    store_row<EPI, NI>(C, ldc, b.row0 + row, wc0, N, acc[i], bias, row < b.Mg, vec, wide, fq);
+  }
 }
 
 // split-K reduction + epilogue: one thread per output element group of 4 columns
@@ -379,6 +501,39 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(void* __restr
                       int groups, hipStream_t st
 #define DLI_GEMM_PASS A, lda, W, ldw, C, ldc, M, N, K, splits, bias, ws, go, groups, st
 constexpr int DLI_NOT_MINE = -0x4d494e45;
+
+// The launcher of every kernel with the (A, lda, W, ldw, C, ldc, M, N, K, k_split_len, bias,
+// ws, group_off) signature: BM x BN tiles on grid (tiles, splits, groups), LDS bytes of
+// dynamic LDS (> 64 KiB needs the opt-in, once per kernel), then the split-K reduce unless
+// C == nullptr (the partial slabs are left for a fused consumer, fused_reduce.hip). SILU_N:
+// the SiLU*up epilogue needs N to be a multiple of it; 0 = this tile has no SiLU epilogue
+// (a wave's column range does not hold whole gate/up pairs).
+template <auto KERNEL, int EPI, int BM, int BN, int THREADS, size_t LDS, int SILU_N>
+static int launch_gemm(DLI_GEMM_ARGS) {
+  if (EPI == EPI_SILU && (SILU_N == 0 || N % (SILU_N ? SILU_N : 1)))
+    return (int)hipErrorInvalidValue;
+  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  int ksl = K / splits;
+  ksl = (ksl / BK) * BK;
+  if (ksl * splits != K) return (int)hipErrorInvalidValue;
+  static bool attr_done = false;
+  if (!attr_done) {
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    if (e != hipSuccess) return (int)e;
+    attr_done = true;
+  }
+  KERNEL<<<dim3(tiles, splits, groups), THREADS, LDS, st>>>(
+      (const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K, ksl, (const u16*)bias, (float*)ws,
+      go);
+  if (splits > 1 && C != nullptr) {
+    const int outN = (EPI == EPI_SILU) ? N / 2 : N;
+    const long total = (long)M * outN;
+    splitk_reduce_kernel<EPI><<<(int)((total + 255) / 256), 256, 0, st>>>(
+        C, ldc, (const float*)ws, M, N, splits, (const u16*)bias);
+  }
+  DLI_RETURN_LAUNCH();
+}
 
 int gemm_tiles_dispatch(int epi, int tile_cfg, DLI_GEMM_ARGS);
 int gemm_8p_dispatch(int epi, int tile_cfg, DLI_GEMM_ARGS);

@@ -1,5 +1,6 @@
-// Generic LDS-tiled MFMA GEMM family (tile ids 0-21, 23-25, 60-61): WM x WN waves, BM x BN x 64
-// block tiles, 2 or 3 LDS stages filled by LDS-DMA. Split-K writes fp32 slabs for the fused
+// Generic LDS-tiled MFMA GEMM family (family "tiles" of ops/gemm.py's TILE_TABLE, the one
+// list of tile ids; dispatch_tiles below is its C++ side): WM x WN waves, BM x BN x 64 block
+// tiles, 2 or 3 LDS stages filled by LDS-DMA. Split-K writes fp32 slabs for the fused
 // consumers (fused_reduce.hip) or reduces them with splitk_reduce_kernel.
 #include "gemm_common.h"
 
@@ -15,24 +16,11 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
   constexpr int BUF = A_BYTES + W_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  // ---- tile coordinates
-  int row0 = 0, Mg = M;
-  const u16* Wg = W;
-  if (group_off != nullptr) {
-    row0 = group_off[blockIdx.z];
-    Mg = group_off[blockIdx.z + 1] - row0;
-    Wg = W + (long)blockIdx.z * N * ldw;
-  }
-  const int tiles_m = (M + BM - 1) / BM;           // M = max rows per group in grouped mode
-  const int tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n;
-  int tile, ks;
-  split_tile(nwg, group_off != nullptr, tile, ks);
-  const int tn = tile / tiles_m, tm = tile % tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
+  // ---- tile coordinates (n-major tile order)
+  const BlockCoord bc = block_coord<BM, BN, 1>(W, ldw, M, N, K, k_split_len, group_off);
+  const int row0 = bc.row0, Mg = bc.Mg, m0 = bc.m0, n0 = bc.n0, kb = bc.kb, nk = bc.nk;
+  const u16* Wg = bc.Wg;
   if (m0 >= Mg) return;                             // grouped: empty tile (block-uniform)
-  const int kb = ks * k_split_len;
-  const int nk = min(k_split_len, K - kb) / BK;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -91,28 +79,28 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
 #pragma unroll
   for (int j = 0; j < NI; ++j) w_row[j] = wn * TN + j * 16 + fr;
 
-  auto compute = [&](int buf) {
+  // every fragment of K half kk of the K-tile in buffer buf
+  auto read_frags = [&](int buf, int kk, bf16x8 (&af)[MI], bf16x8 (&bfr)[NI]) {
     const char* abuf = smem + buf * BUF;
     const char* wbuf = abuf + A_BYTES;
 #pragma unroll
+    for (int i = 0; i < MI; ++i) af[i] = read_frag(abuf, a_row[i], kk, fq);
+#pragma unroll
+    for (int j = 0; j < NI; ++j) bfr[j] = read_frag(wbuf, w_row[j], kk, fq);
+  };
+  auto mfmas = [&](const bf16x8 (&af)[MI], const bf16x8 (&bfr)[NI]) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+  };
+  auto compute = [&](int buf) {
+#pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const int c = kk * 4 + fq;
       bf16x8 af[MI], bfr[NI];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int r = a_row[i];
-        af[i] = *reinterpret_cast<const bf16x8*>(abuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int r = w_row[j];
-        bfr[j] = *reinterpret_cast<const bf16x8*>(wbuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+      read_frags(buf, kk, af, bfr);
+      mfmas(af, bfr);
     }
   };
 
@@ -149,43 +137,20 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     static_assert(WM == 2 && WN == 4 && NS == 3, "staggered schedule: 2 x 4 waves, 3 stages");
     constexpr int INSTR = A_INSTR + W_INSTR;
     const int g = __builtin_amdgcn_readfirstlane(wid) >> 2;
-    auto barrier = [&]() {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("" ::: "memory");
-    };
     if (nk > 0) stage(0, 0);
     if (nk > 1) { stage(1, 1); wait_vmcnt<INSTR>(); }
     else wait_vmcnt<0>();
-    barrier();
+    raw_barrier();
     if (g == 1) {                                    // stagger: group 1 runs one segment behind
-      barrier();
+      raw_barrier();
       __builtin_amdgcn_s_setprio(1);                 // static priority for the younger half
     }
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
       // ---- LOAD
-      const char* abuf = smem + cur * BUF;
-      const char* wbuf = abuf + A_BYTES;
       bf16x8 af[2][MI], bfr[2][NI];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int c = kk * 4 + fq;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const int r = a_row[i];
-          af[kk][i] =
-              *reinterpret_cast<const bf16x8*>(abuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-          const int r = w_row[j];
-          bfr[kk][j] =
-              *reinterpret_cast<const bf16x8*>(wbuf + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        }
-      }
+      read_frags(cur, 0, af[0], bfr[0]);
+      read_frags(cur, 1, af[1], bfr[1]);
       if (kt + 2 < nk) {
         int nb = cur + 2;
         if (nb >= NS) nb -= NS;
@@ -194,21 +159,15 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
       } else {
         wait_vmcnt<0>();
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): this segment's reads done
-      barrier();
+      lgkmcnt0();                                    // this segment's reads done
+      raw_barrier();
       // ---- MATRIX
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-            acc[i][j] =
-                __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[kk][j], af[kk][i], acc[i][j], 0, 0, 0);
-      barrier();
+      mfmas(af[0], bfr[0]);
+      mfmas(af[1], bfr[1]);
+      raw_barrier();
       cur = (cur + 1 == NS) ? 0 : cur + 1;
     }
-    if (g == 0) barrier();                           // balance group 1's stagger barrier
+    if (g == 0) raw_barrier();                       // balance group 1's stagger barrier
   } else if (NS == 2) {
     // 2 LDS buffers: the next tile's DMA overlaps this tile's MFMAs; drained every K-step
     if (nk > 0) stage(0, 0);
@@ -237,7 +196,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     for (int kt = 0; kt < nk; ++kt) {
       const int ahead = min(nk - 1 - kt, NS - 2);     // tiles issued after kt (uniform)
       wait_ahead<INSTR, NS - 2>(ahead);
-      __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
+      lgkmcnt0();
       __builtin_amdgcn_s_barrier();
       if (kt + NS - 1 < nk) {
         int nb = cur + NS - 1;
@@ -252,9 +211,12 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
 
   // ---- epilogue (transposed accumulators):
   // acc[i][j][r] = C[m0 + wm*TM + 16i + fr][n0 + wn*TN + 16j + 4fq + r]
+  // The text of gemm_epilogue (gemm_common.h), kept inline: through the shared function hipcc
+  // allocated this kernel's registers differently (up to +12 / -16 VGPRs over 117
+  // instantiations, profiles/r8/README.md)
   const bool split = gridDim.y > 1;
   if (split) {
-    float* slab = ws + (long)ks * M * N;
+    float* slab = ws + (long)bc.ks * M * N;
     const int sm = g_slab_store;
     const bool vec = (N & 3) == 0;
     const int col0 = n0 + wn * TN;
@@ -309,32 +271,10 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
 }
 
 template <int BM, int BN, int EPI, int NS, int WM = 2, int WN = 2, int STAG = 0>
-static int launch_cfg(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
-                      int N, int K, int splits, const void* bias, void* ws,
-                      const int* group_off, int groups, hipStream_t st) {
-  if (EPI == EPI_SILU && (BN / WN) % 32) return (int)hipErrorInvalidValue;  // gate/up pairs
-  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  int ksl = K / splits;
-  ksl = (ksl / BK) * BK;
-  if (ksl * splits != K) return (int)hipErrorInvalidValue;
-  const size_t lds = NS * (size_t)(BM + BN) * BK * 2;
-  static bool attr_done = false;                   // > 64 KiB dynamic LDS needs the opt-in
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  dim3 grid(tiles, splits, groups);
-  gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG><<<grid, 64 * WM * WN, lds, st>>>(
-      (const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K, ksl, (const u16*)bias,
-      (float*)ws, group_off);
-  if (splits > 1 && C != nullptr) {       // C == nullptr: leave the fp32 partial slabs for a
-    const int outN = (EPI == EPI_SILU) ? N / 2 : N;   // fused consumer (fused_reduce.hip)
-    const long total = (long)M * outN;
-    splitk_reduce_kernel<EPI><<<(int)((total + 255) / 256), 256, 0, st>>>(
-        C, ldc, (const float*)ws, M, N, splits, (const u16*)bias);
-  }
-  DLI_RETURN_LAUNCH();
+static int launch_cfg(DLI_GEMM_ARGS) {
+  // SiLU*up pairs gate/up blocks inside a wave's column range: a multiple of 32 columns
+  return launch_gemm<gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG>, EPI, BM, BN, 64 * WM * WN,
+                     NS * (size_t)(BM + BN) * BK * 2, (BN / WN) % 32 ? 0 : 32>(DLI_GEMM_PASS);
 }
 
 template <int EPI>

@@ -148,7 +148,7 @@ def test_gemm_4wave_persistent(gpu, M, N, K, epi):
                                        (1100, 4096, 14336, "none"), (777, 50257, 4096, "f32"),
                                        (300, 2304, 768, "bias_gelu")])
 def test_gemm_4wave_256(gpu, M, N, K, epi, tile):
-    """The one-wave-per-SIMD 256x256 kernel (tiles 34-37: AGPR-pinned accumulators, buffer
+    """The one-wave-per-SIMD 256x256 kernel (tiles 34, 41, 45: AGPR-pinned accumulators, buffer
     LDS-DMA with range-checked rows) at the prefill token buckets of the Llama-3-8B
     projections (QKV / O / gate-up / down), a decode batch, partial row and column tiles
     (M = 1100 / 777 / 300, N = 50257) and every epilogue, split-K 1/2/4, against the fp32
