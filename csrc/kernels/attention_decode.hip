@@ -374,14 +374,45 @@ __global__ void __launch_bounds__(256) decode_attn_wg_kernel(
 // trip per 32-token tile): wave 0 writes the new k/v row, every wave builds the Q fragments,
 // wave w takes the w-th quarter of the context's tiles, and the four partial (m, l, O) merge
 // through LDS (the V-tile rows are reused for the O partials).
-template <int SPL, int WPI, bool S16 = false>
+//
+// X (dli_decode_attention_fused_x, the Qwen families): a QKV bias [N] (or null) is added to
+// the fp32 slab sum before its rounding to bf16 (Qwen2); then every q head and the k row are
+// RMS-normalised over their 128 dims with q_norm_w / k_norm_w (or null) and rounded to bf16
+// before the rotation (Qwen3). The rounding points are those of dli_splitk_rope_cache_x. A
+// query head's 128 dims sit in the 4 lanes col + 16 grp, so its sum of squares is the xor-16
+// and xor-32 shuffles; the bf16 q values wait in the fragment registers themselves between
+// the two passes (no extra VGPRs live across the reduction; without norm weights the second
+// pass multiplies by 1, which is exact). The k row (dims lane, lane + 64) is one wave
+// reduction. One form serves bias-only and norm models: as a form of its own the bias-only
+// prologue spilled (profiles/qwen/README.md).
+// The extras travel as one trailing kernel argument, empty for the plain forms, which keep
+// their argument list and their code.
+template <bool X>
+struct DecodeQkvExtras {
+  const u16* bias;
+  const u16* q_norm_w;
+  const u16* k_norm_w;
+  float qk_eps;
+};
+template <>
+struct DecodeQkvExtras<false> {};
+
+template <int SPL, int WPI, bool S16 = false, bool X = false>
 __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     u16* __restrict__ out, const void* __restrict__ src, int N,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
     const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ context_lens,
-    int B, int hq, int hkv, int block_size, float scale_log2, int window) {
+    int B, int hq, int hkv, int block_size, float scale_log2, int window,
+    const DecodeQkvExtras<X> ex) {
   constexpr int HD = 128, HALF = 64, KK = HD / 32, VROW = HD + 16, DB = HD / 16;
+  [[maybe_unused]] const u16* bias = nullptr;
+  [[maybe_unused]] const u16* q_norm_w = nullptr;
+  [[maybe_unused]] const u16* k_norm_w = nullptr;
+  [[maybe_unused]] float qk_eps = 0.f;
+  if constexpr (X) {
+    bias = ex.bias; q_norm_w = ex.q_norm_w; k_norm_w = ex.k_norm_w; qk_eps = ex.qk_eps;
+  }
   // SPL > 0: src = the QKV GEMM's fp32 split-K slabs [SPL, B, N]; SPL == 0: the bf16 QKV rows
   // [B, N] of an unsplit GEMM (the same prologue minus the slab sum)
   // S16: the slabs are fp16 x 1/16 (EPI_SLAB16), read as 16-bit words
@@ -391,7 +422,9 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
   static_assert(WPI == 1 || WPI == DEC_WAVES, "one item per wave or per workgroup");
   __shared__ __attribute__((aligned(16))) u16 vtile_all[DEC_WAVES][DEC_TILE * VROW];
   __shared__ float ml_all[WPI > 1 ? WPI : 1][16][2];
-  const int wv = threadIdx.x >> 6;
+  // X: the wave index in a scalar register (kept in a VGPR across the tile loop it was the
+  // one value the 4-slab fp32 form spilled); the plain forms keep their code
+  const int wv = X ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
   u16* vt = vtile_all[wv];
   const int lane = threadIdx.x & 63;
   const int item = WPI > 1 ? (int)blockIdx.x : (int)blockIdx.x * DEC_WAVES + wv;
@@ -407,6 +440,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
   // col of the group, dims 32kk + 8grp .. +7 (kk < 2: first half, its RoPE partner is
   // fragment kk + 2 of the same lane)
   bf16x8 qf[KK];
+  [[maybe_unused]] float qss = 0.f;           // X: this lane's share of the head's squares
   if (col < G) {
     const float* qp = ws + rowoff + (long)(kvh * G + col) * HD;
 #pragma unroll
@@ -445,12 +479,32 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
         x2[0] += c0.x; x2[1] += c0.y; x2[2] += c0.z; x2[3] += c0.w;
         x2[4] += c1.x; x2[5] += c1.y; x2[6] += c1.z; x2[7] += c1.w;
       }
+      if constexpr (X) {
+        if (bias != nullptr) {
+          const u16* bq = bias + (long)(kvh * G + col) * HD;
+          float b1[8], b2[8];
+          load8(bq + d1, b1);
+          load8(bq + HALF + d1, b2);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float q1 = bf2f(f2bf(x1[j])), q2 = bf2f(f2bf(x2[j]));
-        const float co = cs[d1 + j], si = cs[HALF + d1 + j];
-        qf[kp2][j] = (__bf16)(q1 * co - q2 * si);
-        qf[kp2 + 2][j] = (__bf16)(q2 * co + q1 * si);
+          for (int j = 0; j < 8; ++j) { x1[j] += b1[j]; x2[j] += b2[j]; }
+        }
+      }
+      if constexpr (X) {                      // pass 1: the bf16 q, parked in the fragments
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          qf[kp2][j] = (__bf16)x1[j];
+          qf[kp2 + 2][j] = (__bf16)x2[j];
+          const float q1 = (float)qf[kp2][j], q2 = (float)qf[kp2 + 2][j];
+          qss += q1 * q1 + q2 * q2;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float q1 = bf2f(f2bf(x1[j])), q2 = bf2f(f2bf(x2[j]));
+          const float co = cs[d1 + j], si = cs[HALF + d1 + j];
+          qf[kp2][j] = (__bf16)(q1 * co - q2 * si);
+          qf[kp2 + 2][j] = (__bf16)(q2 * co + q1 * si);
+        }
       }
     }
   } else {
@@ -458,6 +512,32 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     for (int kk = 0; kk < KK; ++kk) {
       uint4 z = make_uint4(0, 0, 0, 0);
       qf[kk] = *reinterpret_cast<bf16x8*>(&z);
+    }
+  }
+  if constexpr (X) {                          // pass 2: normalise, then rotate
+    // the 4 lanes of a head (col + 16 grp) take the same side of col < G; every lane shuffles
+    const bool nrm = q_norm_w != nullptr;
+    qss += __shfl_xor(qss, 16, 64);
+    qss += __shfl_xor(qss, 32, 64);
+    if (col < G) {
+      const float rstd = nrm ? rsqrtf(qss / HD + qk_eps) : 1.f;
+#pragma unroll
+      for (int kp2 = 0; kp2 < KK / 2; ++kp2) {
+        const int d1 = 32 * kp2 + 8 * grp;
+        float w1[8] = {1, 1, 1, 1, 1, 1, 1, 1}, w2[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+        if (nrm) {
+          load8(q_norm_w + d1, w1);
+          load8(q_norm_w + HALF + d1, w2);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float q1 = bf2f(f2bf((float)qf[kp2][j] * rstd * w1[j]));
+          const float q2 = bf2f(f2bf((float)qf[kp2 + 2][j] * rstd * w2[j]));
+          const float co = cs[d1 + j], si = cs[HALF + d1 + j];
+          qf[kp2][j] = (__bf16)(q1 * co - q2 * si);
+          qf[kp2 + 2][j] = (__bf16)(q2 * co + q1 * si);
+        }
+      }
     }
   }
   // the block-table window too: every load the tile loop's first tile waits on except the
@@ -495,7 +575,22 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
       k1 = bf2f(kr[lane]); k2 = bf2f(kr[HALF + lane]);
       v1 = bf2f(vr[lane]); v2 = bf2f(vr[HALF + lane]);
     }
+    if constexpr (X) {
+      if (bias != nullptr) {
+        const u16* bk = bias + (long)(hq + kvh) * HD;
+        const u16* bv = bias + (long)(hq + hkv + kvh) * HD;
+        k1 += bf2f(bk[lane]); k2 += bf2f(bk[HALF + lane]);
+        v1 += bf2f(bv[lane]); v2 += bf2f(bv[HALF + lane]);
+      }
+    }
     k1 = bf2f(f2bf(k1)); k2 = bf2f(f2bf(k2));
+    if constexpr (X) {                        // the whole wave is here (slot is per sequence)
+      if (k_norm_w != nullptr) {
+        const float rstd = rsqrtf(wave_sum(k1 * k1 + k2 * k2) / HD + qk_eps);
+        k1 = bf2f(f2bf(k1 * rstd * bf2f(k_norm_w[lane])));
+        k2 = bf2f(f2bf(k2 * rstd * bf2f(k_norm_w[HALF + lane])));
+      }
+    }
     const float co = cs[lane], si = cs[HALF + lane];
     const int blk = slot / block_size, off = slot - blk * block_size;
     const long dst = (((long)blk * hkv + kvh) * block_size + off) * HD;
@@ -893,28 +988,45 @@ extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, cons
 // with splits == 0 the bf16 QKV rows [B, (hq + 2 hkv) * 128] of an unsplit GEMM.
 // fmt: 0 = fp32 slabs (or the bf16 rows when splits == 0), 1 = fp16 x 1/16 slabs (EPI_SLAB16)
 // window > 0: sliding-window attention (decode_win_lo)
-extern "C" int dli_decode_attention_fused_win(void* out, const void* ws, int splits,
-                                              const int* positions, const int* slot_mapping,
-                                              const float* cos_sin, void* k_cache,
-                                              void* v_cache, const int* block_tables,
-                                              int max_blocks, const int* context_lens, int B,
-                                              int hq, int hkv, int hd, int block_size,
-                                              float scale, int fmt, int window,
-                                              hipStream_t st) {
+// bias [N] / q_norm_w, k_norm_w [128] (the two together): bf16, 16-B aligned, or null;
+// all null = dli_decode_attention_fused_win
+extern "C" int dli_decode_attention_fused_x(void* out, const void* ws, int splits,
+                                            const int* positions, const int* slot_mapping,
+                                            const float* cos_sin, void* k_cache, void* v_cache,
+                                            const int* block_tables, int max_blocks,
+                                            const int* context_lens, int B, int hq, int hkv,
+                                            int hd, int block_size, float scale, int fmt,
+                                            int window, const void* bias, const void* q_norm_w,
+                                            const void* k_norm_w, float qk_eps,
+                                            hipStream_t st) {
   if (B <= 0) return 0;
   if (window < 0) window = 0;
   if (hd != 128 || hq % hkv || hq / hkv > 16 || block_size % 16 ||
       (splits != 0 && splits != 2 && splits != 4) || fmt < 0 || fmt > 1 ||
       (fmt == 1 && splits == 0))
     return (int)hipErrorInvalidValue;
+  if ((q_norm_w == nullptr) != (k_norm_w == nullptr) ||
+      (((uintptr_t)bias | (uintptr_t)q_norm_w | (uintptr_t)k_norm_w) & 15))
+    return (int)hipErrorInvalidValue;
+  const bool extras = bias != nullptr || q_norm_w != nullptr;
   const int N = (hq + 2 * hkv) * hd;
   const float scale_log2 = scale * 1.4426950408889634f;
   const long items = (long)B * hkv;
   const bool per_wg = wg_form(items);
   dim3 grid((int)(per_wg ? items : (items + DEC_WAVES - 1) / DEC_WAVES));
-#define DLI_DAF(S, W, F) decode_attn_fused_kernel<S, W, F><<<grid, 64 * DEC_WAVES, 0, st>>>(   \
+#define DLI_DAFX(S, W, F, X, ...) decode_attn_fused_kernel<S, W, F, X>                        \
+      <<<grid, 64 * DEC_WAVES, 0, st>>>(                                                     \
       (u16*)out, ws, N, positions, slot_mapping, cos_sin, (u16*)k_cache, (u16*)v_cache,      \
-      block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window)
+      block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window,    \
+      DecodeQkvExtras<X>{__VA_ARGS__})
+#define DLI_DAF(S, W, F)                                                                      \
+  do {                                                                                        \
+    if (extras)                                                                               \
+      DLI_DAFX(S, W, F, true, (const u16*)bias, (const u16*)q_norm_w, (const u16*)k_norm_w,   \
+               qk_eps);                                                                       \
+    else                                                                                      \
+      DLI_DAFX(S, W, F, false);                                                               \
+  } while (0)
   if (per_wg) {
     if (splits == 0) DLI_DAF(0, DEC_WAVES, false);
     else if (splits == 2) { if (fmt) DLI_DAF(2, DEC_WAVES, true); else DLI_DAF(2, DEC_WAVES, false); }
@@ -925,7 +1037,22 @@ extern "C" int dli_decode_attention_fused_win(void* out, const void* ws, int spl
     else { if (fmt) DLI_DAF(4, 1, true); else DLI_DAF(4, 1, false); }
   }
 #undef DLI_DAF
+#undef DLI_DAFX
   DLI_RETURN_LAUNCH();
+}
+
+extern "C" int dli_decode_attention_fused_win(void* out, const void* ws, int splits,
+                                              const int* positions, const int* slot_mapping,
+                                              const float* cos_sin, void* k_cache,
+                                              void* v_cache, const int* block_tables,
+                                              int max_blocks, const int* context_lens, int B,
+                                              int hq, int hkv, int hd, int block_size,
+                                              float scale, int fmt, int window,
+                                              hipStream_t st) {
+  return dli_decode_attention_fused_x(out, ws, splits, positions, slot_mapping, cos_sin,
+                                      k_cache, v_cache, block_tables, max_blocks, context_lens,
+                                      B, hq, hkv, hd, block_size, scale, fmt, window, nullptr,
+                                      nullptr, nullptr, 0.f, st);
 }
 
 extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,

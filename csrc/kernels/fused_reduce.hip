@@ -4,6 +4,7 @@
 //  dli_splitk_add_rmsnorm : out = rmsnorm(residual += sum_s P_s) * w     (O-proj, down-proj)
 //                           (w == null: residual += sum_s P_s only, for a stage's last layer)
 //  dli_splitk_rope_cache  : qkv = bf16(sum_s P_s); RoPE on q,k in place; k,v -> paged cache
+//  dli_splitk_rope_cache_x: the same with a QKV bias and / or a per-head q,k RMSNorm (Qwen)
 //
 // P_s are the [M, N] slabs written by a GEMM called with C == nullptr: fp32, or (fmt 1, the
 // EPI_SLAB16 epilogue of the MFMA families) fp16 scaled by 1/16. The sum is fp32 in slab
@@ -236,12 +237,19 @@ extern "C" int dli_splitk_add_rmsnorm(void* out, void* residual, const float* ws
 // one lane: 8 dims of the first half of a head + the matching 8 of the second half. SPL > 0:
 // compile-time split count, every partial's loads issued before the first add (and the
 // position / cos-sin loads ahead of them); SPL == 0: runtime loop.
-template <int SPL, bool S16 = false>
-__global__ void __launch_bounds__(256) splitk_rope_cache_kernel(
+//
+// X (dli_splitk_rope_cache_x, the Qwen families): bias [N] (or null) is added to the fp32
+// slab sum before the one rounding that stands for the GEMM output; then every q and k head
+// is RMS-normalised over its hd dims with q_norm_w / k_norm_w [hd] (or null) and rounded to
+// bf16 before the rotation (v: bias only). The hd / 16 lanes of a head are consecutive,
+// aligned in the wave and leave together at the gid guard: log2(hd / 16) xor-shuffles.
+template <int SPL, bool S16, bool X>
+__device__ __forceinline__ void splitk_rope_cache_body(
     u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
     const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
-    int hq, int hkv, int hd, int block_size, int use_rope) {
+    int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
+    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps) {
   const int lanes_per_head = hd >> 4;
   const int heads = hq + 2 * hkv;
   const long total = (long)T * heads * lanes_per_head;
@@ -298,8 +306,38 @@ __global__ void __launch_bounds__(256) splitk_rope_cache_kernel(
       add4(x2, p2[0], p2[1]);
     }
   }
+  if constexpr (X) {
+    if (bias != nullptr) {
+      float b1[8], b2[8];
+      load8(bias + col1, b1);
+      load8(bias + col2, b2);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { x1[j] += b1[j]; x2[j] += b2[j]; }
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) { x1[j] = bf2f(f2bf(x1[j])); x2[j] = bf2f(f2bf(x2[j])); }
+  if constexpr (X) {
+    if (q_norm_w != nullptr) {
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += x1[j] * x1[j] + x2[j] * x2[j];
+      // every lane of the wave that passed the guard shuffles (v heads too, unused there)
+      for (int o = 1; o < lanes_per_head; o <<= 1) ss += __shfl_xor(ss, o, 64);
+      if (is_q || is_k) {
+        const float rstd = rsqrtf(ss / hd + qk_eps);
+        const u16* wn = is_q ? q_norm_w : k_norm_w;
+        float w1[8], w2[8];
+        load8(wn + d0, w1);
+        load8(wn + half + d0, w2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          x1[j] = bf2f(f2bf(x1[j] * rstd * w1[j]));
+          x2[j] = bf2f(f2bf(x2[j] * rstd * w2[j]));
+        }
+      }
+    }
+  }
   if (rope) {
     const float* cs = cos_sin + (long)pos * hd;
 #pragma unroll
@@ -324,20 +362,61 @@ __global__ void __launch_bounds__(256) splitk_rope_cache_kernel(
   store8(dst + half + d0, x2);
 }
 
-extern "C" int dli_splitk_rope_cache(void* qkv, const float* ws, int splits, int T, int N,
-                                     const int* positions, const int* slot_mapping,
-                                     const float* cos_sin, void* k_cache, void* v_cache, int hq,
-                                     int hkv, int hd, int block_size, int use_rope, int fmt,
-                                     hipStream_t st) {
+template <int SPL, bool S16 = false>
+__global__ void __launch_bounds__(256) splitk_rope_cache_kernel(
+    u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
+    const int* __restrict__ positions, const int* __restrict__ slot_mapping,
+    const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
+    int hq, int hkv, int hd, int block_size, int use_rope) {
+  splitk_rope_cache_body<SPL, S16, false>(qkv, ws, splits, T, N, positions, slot_mapping,
+                                          cos_sin, k_cache, v_cache, hq, hkv, hd, block_size,
+                                          use_rope, nullptr, nullptr, nullptr, 0.f);
+}
+
+template <int SPL, bool S16 = false>
+__global__ void __launch_bounds__(256) splitk_rope_cache_x_kernel(
+    u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
+    const int* __restrict__ positions, const int* __restrict__ slot_mapping,
+    const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
+    int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
+    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps) {
+  splitk_rope_cache_body<SPL, S16, true>(qkv, ws, splits, T, N, positions, slot_mapping,
+                                         cos_sin, k_cache, v_cache, hq, hkv, hd, block_size,
+                                         use_rope, bias, q_norm_w, k_norm_w, qk_eps);
+}
+
+// bias / q_norm_w / k_norm_w: bf16, 16-B aligned, or null (the two norm weights together);
+// all null = dli_splitk_rope_cache
+extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, int T, int N,
+                                       const int* positions, const int* slot_mapping,
+                                       const float* cos_sin, void* k_cache, void* v_cache,
+                                       int hq, int hkv, int hd, int block_size, int use_rope,
+                                       int fmt, const void* bias, const void* q_norm_w,
+                                       const void* k_norm_w, float qk_eps, hipStream_t st) {
   if (T <= 0) return 0;
   if (hd % 16 || N != (hq + 2 * hkv) * hd || fmt < 0 || fmt > 1 ||
       (fmt == 1 && splits != 2 && splits != 4 && splits != 8))
     return (int)hipErrorInvalidValue;
   const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
   const int blocks = (int)((total + 255) / 256);
-#define DLI_SRC(S, F) splitk_rope_cache_kernel<S, F><<<blocks, 256, 0, st>>>(             \
-      (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (u16*)k_cache,        \
-      (u16*)v_cache, hq, hkv, hd, block_size, use_rope)
+  const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
+  const int lph = hd / 16;                       // the head's lanes must be a shuffle group
+  if (extras && ((q_norm_w == nullptr) != (k_norm_w == nullptr) ||
+                 (q_norm_w != nullptr && ((lph & (lph - 1)) || lph > 64)) ||
+                 (((uintptr_t)bias | (uintptr_t)q_norm_w | (uintptr_t)k_norm_w) & 15)))
+    return (int)hipErrorInvalidValue;
+#define DLI_SRC(S, F)                                                                       \
+  do {                                                                                      \
+    if (extras)                                                                             \
+      splitk_rope_cache_x_kernel<S, F><<<blocks, 256, 0, st>>>(                             \
+          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (u16*)k_cache,     \
+          (u16*)v_cache, hq, hkv, hd, block_size, use_rope, (const u16*)bias,               \
+          (const u16*)q_norm_w, (const u16*)k_norm_w, qk_eps);                              \
+    else                                                                                    \
+      splitk_rope_cache_kernel<S, F><<<blocks, 256, 0, st>>>(                               \
+          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (u16*)k_cache,     \
+          (u16*)v_cache, hq, hkv, hd, block_size, use_rope);                                \
+  } while (0)
   if (fmt == 1) {
     switch (splits) {
       case 2: DLI_SRC(2, true); break;
@@ -353,4 +432,14 @@ extern "C" int dli_splitk_rope_cache(void* qkv, const float* ws, int splits, int
   }
 #undef DLI_SRC
   DLI_RETURN_LAUNCH();
+}
+
+extern "C" int dli_splitk_rope_cache(void* qkv, const float* ws, int splits, int T, int N,
+                                     const int* positions, const int* slot_mapping,
+                                     const float* cos_sin, void* k_cache, void* v_cache, int hq,
+                                     int hkv, int hd, int block_size, int use_rope, int fmt,
+                                     hipStream_t st) {
+  return dli_splitk_rope_cache_x(qkv, ws, splits, T, N, positions, slot_mapping, cos_sin,
+                                 k_cache, v_cache, hq, hkv, hd, block_size, use_rope, fmt,
+                                 nullptr, nullptr, nullptr, 0.f, st);
 }

@@ -16,7 +16,7 @@ from typing import Optional
 @dataclass(frozen=True)
 class ModelConfig:
     name: str
-    arch: str                 # "llama" (llama / mixtral family) or "gpt2"
+    arch: str                 # "llama" (llama / mistral / mixtral / qwen family) or "gpt2"
     hidden_size: int
     num_layers: int
     num_heads: int
@@ -38,6 +38,10 @@ class ModelConfig:
     # sliding-window attention (Mistral): a query sees the last ``sliding_window`` keys up to
     # and including its own, in every layer; 0 = full attention
     sliding_window: int = 0
+    # Qwen3: per-head RMSNorm (weights q_norm / k_norm [head_dim], eps = norm_eps) on every
+    # query and key head before RoPE; Qwen2 / 2.5: a bias on the fused QKV projection (bqkv)
+    qk_norm: bool = False
+    qkv_bias: bool = False
 
     @property
     def is_moe(self) -> bool:
@@ -64,7 +68,10 @@ class ModelConfig:
         mlp = 3 * d * f
         if self.is_moe:
             mlp = self.num_experts * mlp + d * self.num_experts
-        return attn + mlp + 2 * d
+        extra = 2 * self.head_dim if self.qk_norm else 0       # q_norm, k_norm
+        if self.qkv_bias:
+            extra += self.qkv_size
+        return attn + mlp + 2 * d + extra
 
     def embed_param_count(self) -> int:
         n = self.vocab_size * self.hidden_size
@@ -124,6 +131,18 @@ MISTRAL_7B = ModelConfig(
     max_position=32768, rope_theta=10000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2,
     sliding_window=4096)
 
+# Qwen3-8B: Llama layers plus the per-head q/k RMSNorm; Qwen2.5-7B: plus the QKV bias
+QWEN3_8B = ModelConfig(
+    name="qwen3-8b", arch="llama", hidden_size=4096, num_layers=36, num_heads=32, num_kv_heads=8,
+    head_dim=128, intermediate_size=12288, vocab_size=151936, max_position=40960,
+    rope_theta=1e6, norm_eps=1e-6, bos_token_id=151643, eos_token_id=151645, qk_norm=True)
+
+QWEN25_7B = ModelConfig(
+    name="qwen2.5-7b", arch="llama", hidden_size=3584, num_layers=28, num_heads=28,
+    num_kv_heads=4, head_dim=128, intermediate_size=18944, vocab_size=152064,
+    max_position=131072, rope_theta=1e6, norm_eps=1e-6, bos_token_id=151643,
+    eos_token_id=151643, qkv_bias=True)
+
 # Tiny variants: same code paths, test-sized. Shapes keep the hardware-friendly
 # multiples (head_dim 64/128, hidden multiple of 256) so HIP kernels see real layouts.
 LLAMA_TINY = ModelConfig(
@@ -137,6 +156,13 @@ LLAMA_TINY128 = replace(LLAMA_TINY, name="llama-tiny128", hidden_size=512, num_h
 # sliding-window twins (head dim 64 / 128): a window short enough for tests to cross
 MISTRAL_TINY = replace(LLAMA_TINY, name="mistral-tiny", sliding_window=24)
 MISTRAL_TINY128 = replace(LLAMA_TINY128, name="mistral-tiny128", sliding_window=24)
+
+# Qwen twins: QK-norm at head dim 64; at head dim 128 with q_size (512) != hidden (256) and
+# tied embeddings, like the small Qwen3 checkpoints; the QKV bias at head dim 128
+QWEN3_TINY = replace(LLAMA_TINY, name="qwen3-tiny", qk_norm=True)
+QWEN3_TINY128 = replace(LLAMA_TINY, name="qwen3-tiny128", hidden_size=256, num_heads=4,
+                        num_kv_heads=2, head_dim=128, qk_norm=True, tie_embeddings=True)
+QWEN2_TINY128 = replace(LLAMA_TINY128, name="qwen2-tiny128", qkv_bias=True)
 
 # 8 layers: one per stage of an 8-rank pipeline test
 LLAMA_TINY8 = replace(LLAMA_TINY, name="llama-tiny8", num_layers=8)
@@ -154,7 +180,7 @@ GPT2_TINY = replace(GPT2, name="gpt2-tiny", hidden_size=256, num_layers=2, num_h
 _REGISTRY = {c.name: c for c in
              (GPT2, LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, LLAMA_TINY, LLAMA_TINY128,
               LLAMA_TINY8, MIXTRAL_TINY, MIXTRAL_TINY8E, GPT2_TINY, MISTRAL_7B, MISTRAL_TINY,
-              MISTRAL_TINY128)}
+              MISTRAL_TINY128, QWEN3_8B, QWEN25_7B, QWEN3_TINY, QWEN3_TINY128, QWEN2_TINY128)}
 
 _ALIASES = {
     "openai-community/gpt2": "gpt2",
@@ -171,6 +197,9 @@ _ALIASES = {
     "mistralai/mixtral-8x7b-v0.1": "mixtral-8x7b",
     "mixtral": "mixtral-8x7b",
     "mixtral_8x7b": "mixtral-8x7b",
+    "qwen/qwen3-8b": "qwen3-8b",
+    "qwen/qwen2.5-7b": "qwen2.5-7b",
+    "qwen/qwen2.5-7b-instruct": "qwen2.5-7b",
 }
 
 

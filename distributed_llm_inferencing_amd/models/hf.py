@@ -1,5 +1,6 @@
 """HF checkpoint import: ``save_pretrained`` directories (and hub-cache snapshots) of
-LlamaForCausalLM / MixtralForCausalLM / GPT2LMHeadModel.
+LlamaForCausalLM / MistralForCausalLM / MixtralForCausalLM / Qwen2ForCausalLM /
+Qwen3ForCausalLM / GPT2LMHeadModel.
 
 The reference loads checkpoints with ``AutoModelForCausalLM.from_pretrained(model_name,
 cache_dir=MODEL_CACHE_DIR)`` (``worker/app.py:117-124``) and its sharder shards a loaded HF
@@ -60,7 +61,8 @@ def find_hf_dir(root: str, name: str) -> Optional[Path]:
 
 def config_from_hf(c: dict, name: Optional[str] = None,
                    sliding_window: bool = False) -> ModelConfig:
-    """Map a HF ``config.json`` (llama / mistral / mixtral / gpt2 model types).
+    """Map a HF ``config.json`` (llama / mistral / mixtral / qwen2 / qwen3 / gpt2 model types;
+    qwen3 sets ``qk_norm``, qwen2 — and a qwen3 with ``attention_bias`` — ``qkv_bias``).
     ``sliding_window``: the caller runs the model through ``TransformerLM``, whose attention
     honours ``ModelConfig.sliding_window``: a checkpoint's window (smaller than its
     ``max_position_embeddings``) is kept and the context is the model's own. Without it the
@@ -77,8 +79,15 @@ def config_from_hf(c: dict, name: Optional[str] = None,
             rope_theta=0.0, norm_eps=float(c.get("layer_norm_epsilon", 1e-5)),
             tie_embeddings=True, bos_token_id=int(c.get("bos_token_id", 50256)),
             eos_token_id=_eos(c, 50256))
-    if mt not in ("llama", "mistral", "mixtral"):
-        raise ValueError(f"unsupported HF model_type '{mt}' (llama, mistral, mixtral, gpt2)")
+    if mt not in ("llama", "mistral", "mixtral", "qwen2", "qwen3"):
+        raise ValueError(f"unsupported HF model_type '{mt}' "
+                         "(llama, mistral, mixtral, qwen2, qwen3, gpt2)")
+    qwen = mt in ("qwen2", "qwen3")
+    if qwen and c.get("use_sliding_window"):
+        raise ValueError(
+            f"{mt} checkpoint with use_sliding_window=true: it windows only some of its layers "
+            "(max_window_layers / layer_types), and this engine applies one window to every "
+            "layer")
     d, nh = int(c["hidden_size"]), int(c["num_attention_heads"])
     rope = c.get("rope_theta")
     params = c.get("rope_parameters") or {}
@@ -98,7 +107,8 @@ def config_from_hf(c: dict, name: Optional[str] = None,
     # is full attention. A caller that does not opt in gets a full-attention config: full
     # attention equals the windowed one while a sequence fits the window, so the context is
     # capped there instead of silently diverging past it
-    sw = c.get("sliding_window")
+    # Qwen configs carry a sliding_window value next to use_sliding_window=false: not a window
+    sw = None if qwen else c.get("sliding_window")
     window = 0
     if sw and int(sw) < max_pos:
         if sliding_window:
@@ -123,7 +133,8 @@ def config_from_hf(c: dict, name: Optional[str] = None,
         top_k_experts=int(c.get("num_experts_per_tok", 2)),
         tie_embeddings=bool(c.get("tie_word_embeddings", False)),
         bos_token_id=int(c.get("bos_token_id") or 1), eos_token_id=_eos(c, 2),
-        sliding_window=window)
+        sliding_window=window, qk_norm=mt == "qwen3",
+        qkv_bias=mt == "qwen2" or (mt == "qwen3" and bool(c.get("attention_bias", False))))
 
 
 def _eos(c: dict, default: int) -> int:

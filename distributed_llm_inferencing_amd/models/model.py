@@ -1,4 +1,5 @@
-"""Transformer decoder for the Llama-3 / Mixtral / GPT-2 families, pipeline-stage aware.
+"""Transformer decoder for the Llama-3 / Mistral / Mixtral / Qwen2 / Qwen3 / GPT-2 families,
+pipeline-stage aware.
 
 One ``TransformerLM`` instance owns layers ``[layer_start, layer_end)`` of a model plus the
 embedding (first stage) and final norm + LM head + sampler (last stage). It is the
@@ -151,16 +152,21 @@ class TransformerLM:
                 h = ops.add_rmsnorm(pending, residual, lp["attn_norm"], eps)
                 pending = None
             attn = None
+            # Qwen2's QKV bias / Qwen3's per-head q,k RMSNorm: inputs of the same RoPE kernels
+            bqkv = lp["bqkv"] if cfg.qkv_bias else None
+            qkn = (lp["q_norm"], lp["k_norm"], eps) if cfg.qk_norm else None
             if not b.is_prefill:             # decode: reduce + RoPE + KV write + attention fused
                 attn = ops.linear_rope_attention(h, lp["wqkv"], b.positions, b.slot_mapping,
                                                  self.cos_sin, kc, vc, b.block_tables,
                                                  b.context_lens, b.max_context, cfg.num_heads,
                                                  cfg.num_kv_heads, cfg.head_dim, self.scale,
-                                                 window=cfg.sliding_window)
+                                                 window=cfg.sliding_window, bias=bqkv,
+                                                 qk_norm=qkn)
             if attn is None:
                 qkv = ops.linear_rope_cache(h, lp["wqkv"], b.positions, b.slot_mapping,
                                             self.cos_sin, kc, vc, cfg.num_heads,
-                                            cfg.num_kv_heads, cfg.head_dim)
+                                            cfg.num_kv_heads, cfg.head_dim, bias=bqkv,
+                                            qk_norm=qkn)
                 attn = self._attend(qkv, b, kc, vc)
             if cfg.is_moe and self.tp_reduce is None and not defer:
                 # O projection + add + RMSNorm with the MoE gate of its output rows (one

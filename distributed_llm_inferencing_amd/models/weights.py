@@ -4,6 +4,7 @@ Our in-memory layout (all [out, in] row-major like torch Linear, bf16):
 
 llama / mixtral (per layer ``layers.{i}.``):
     attn_norm [D], wqkv [(Hq+2Hkv)*hd, D], wo [D, Hq*hd], mlp_norm [D],
+    (qk_norm, Qwen3) q_norm [hd], k_norm [hd]; (qkv_bias, Qwen2) bqkv [(Hq+2Hkv)*hd]
     dense: w_gu [2F, D] (16-row gate/up interleave, see ops/reference.py), w_down [D, F]
     moe:   router [E, D], w_gu [E, 2F, D], w_down [E, D, F]
 gpt2 (per layer): ln1_w, ln1_b, wqkv [3D, D], bqkv [3D], wo [D, D], bo [D], ln2_w, ln2_b,
@@ -36,6 +37,10 @@ def layer_param_shapes(cfg: ModelConfig, i: int) -> Dict[str, tuple]:
                 p + "w_fc": (f, d), p + "b_fc": (f,), p + "w_proj": (d, f), p + "b_proj": (d,)}
     s = {p + "attn_norm": (d,), p + "wqkv": (cfg.qkv_size, d), p + "wo": (d, cfg.q_size),
          p + "mlp_norm": (d,)}
+    if cfg.qk_norm:
+        s.update({p + "q_norm": (hd,), p + "k_norm": (hd,)})
+    if cfg.qkv_bias:
+        s[p + "bqkv"] = (cfg.qkv_size,)
     if cfg.is_moe:
         e = cfg.num_experts
         s.update({p + "router": (e, d), p + "w_gu": (e, 2 * f, d), p + "w_down": (e, d, f)})
@@ -75,7 +80,8 @@ def stage_param_shapes(cfg: ModelConfig, layer_start: int, layer_end: int, first
 
 
 def _is_norm_weight(name: str) -> bool:
-    return name.endswith(("attn_norm", "mlp_norm", "final_norm", "ln1_w", "ln2_w"))
+    return name.endswith(("attn_norm", "mlp_norm", "final_norm", "ln1_w", "ln2_w", ".q_norm",
+                          ".k_norm"))
 
 
 def _is_bias(name: str) -> bool:
@@ -172,6 +178,13 @@ def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
                                         sd[h + "self_attn.k_proj.weight"],
                                         sd[h + "self_attn.v_proj.weight"]], 0))
         out[p + "wo"] = cv(sd[h + "self_attn.o_proj.weight"])
+        if cfg.qk_norm:                          # Qwen3: per-head q/k RMSNorm weights [hd]
+            out[p + "q_norm"] = cv(sd[h + "self_attn.q_norm.weight"])
+            out[p + "k_norm"] = cv(sd[h + "self_attn.k_norm.weight"])
+        if cfg.qkv_bias:                         # Qwen2: biases of q/k/v, in wqkv's row order
+            out[p + "bqkv"] = cv(torch.cat([sd[h + "self_attn.q_proj.bias"],
+                                            sd[h + "self_attn.k_proj.bias"],
+                                            sd[h + "self_attn.v_proj.bias"]], 0))
         if cfg.is_moe:
             moe = h + "block_sparse_moe."
             if moe + "gate.weight" not in sd:

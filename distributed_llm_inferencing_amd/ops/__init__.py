@@ -342,10 +342,32 @@ def linear_add_rmsnorm(x, w, residual, norm_w, eps, plan: Optional[G.GemmPlan] =
     return out
 
 
+def _qkv_extras(bias, qk_norm, n: int, hd: int):
+    """The optional inputs of the RoPE kernels, checked: ``bias`` [n] (Qwen2's QKV bias) and
+    ``qk_norm`` = (q_w [hd], k_w [hd], eps) (Qwen3's per-head RMSNorm of q and k before the
+    rotation). Returns (bias, q_w, k_w, eps) with None for what is absent."""
+    q_w = k_w = None
+    eps = 0.0
+    if qk_norm is not None:
+        q_w, k_w, eps = qk_norm
+        if q_w.numel() != hd or k_w.numel() != hd:
+            raise ValueError(f"qk_norm weights must have head_dim = {hd} elements")
+    ts = [t for t in (bias, q_w, k_w) if t is not None]
+    if bias is not None and bias.numel() != n:
+        raise ValueError(f"qkv bias must have {n} elements, got {bias.numel()}")
+    if any(t.dtype != torch.bfloat16 or not t.is_contiguous() or t.data_ptr() % 16
+           for t in ts):
+        raise ValueError("qkv bias / qk_norm weights must be contiguous 16-B aligned bf16")
+    return bias, q_w, k_w, float(eps)
+
+
 def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
-                      use_rope: bool = True, plan: Optional[G.GemmPlan] = None):
+                      use_rope: bool = True, plan: Optional[G.GemmPlan] = None, bias=None,
+                      qk_norm=None):
     """qkv = x @ w.T with RoPE applied in place to q,k and k,v written to the paged cache.
-    ``plan`` forces the GEMM plan (the autotuner times QKV candidates with this consumer)."""
+    ``plan`` forces the GEMM plan (the autotuner times QKV candidates with this consumer).
+    ``bias`` / ``qk_norm``: see ``rope_and_cache``; with split-K slabs the bias is added to
+    their fp32 sum, before the one rounding that stands for the GEMM output."""
     if isinstance(x, NormedRows):
         x = x.materialize()
     if plan is None:
@@ -353,9 +375,12 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
     else:
         p = plan if plan.splits > 1 else None
     if p is None:
-        qkv = linear(x, w) if plan is None else _gemm_native(x, w, "none", plan=plan)
+        if plan is None:
+            qkv = linear(x, w, bias)
+        else:
+            qkv = _gemm_native(x, w, "none" if bias is None else "bias", bias=bias, plan=plan)
         rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
-                       use_rope)
+                       use_rope, qk_norm=qk_norm)
         return qkv
     M, K = x.shape
     Nn = w.shape[0]
@@ -363,15 +388,21 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
     fmt = _slab_gemm(x, w, p, ws)
     qkv = torch.empty(M, Nn, dtype=x.dtype, device=x.device)
     bs = k_cache.shape[2] if k_cache is not None else 16
-    _native_call("dli_splitk_rope_cache", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
+    if bias is None and qk_norm is None:
+        _native_call("dli_splitk_rope_cache", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
+                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq, hkv, hd, bs,
+                     int(use_rope), fmt, _st())
+        return qkv
+    bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
+    _native_call("dli_splitk_rope_cache_x", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
                  _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq, hkv, hd, bs,
-                 int(use_rope), fmt, _st())
+                 int(use_rope), fmt, _p(bias), _p(q_w), _p(k_w), eps, _st())
     return qkv
 
 
 def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache,
                           block_tables, context_lens, max_context: int, hq, hkv, hd, scale,
-                          window: int = 0):
+                          window: int = 0, bias=None, qk_norm=None):
     """Decode step, one fused pass after the QKV GEMM: the split-K slabs (or, for an unsplit
     plan, the bf16 QKV rows) are reduced, q and k rotated, k/v written to the paged cache and
     attention computed by ONE kernel per layer (``dli_decode_attention_fused``) instead of
@@ -380,7 +411,8 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     split counts other than 2 / 4, KV-split attention (long contexts at small batch), the
     pipelined long-context kernel, head dim != 128. ``window`` > 0: sliding-window attention;
     the choice between the kernels follows the span a sequence can attend over,
-    min(max_context, window)."""
+    min(max_context, window). ``bias`` / ``qk_norm`` (Qwen2 / Qwen3, see ``rope_and_cache``)
+    are applied by the same kernel's prologue."""
     xr = x.residual if isinstance(x, NormedRows) else x
     if hd != 128 or k_cache is None or not _use_native(xr):
         return None
@@ -397,7 +429,8 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     Nn = w.shape[0]
     fmt = 0
     if p is None:                         # unsplit plan: the prologue reads the bf16 rows
-        src, splits = linear(x, w), 0
+        src, splits = linear(x, w, bias), 0
+        bias = None                       # applied by the GEMM's epilogue
     else:
         src, splits = G.workspace(xr.device, p.splits * B * Nn * 4), p.splits
         if not (isinstance(x, NormedRows)
@@ -406,10 +439,17 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
                 x = x.materialize()
             fmt = _slab_gemm(x, w, p, src)
     out = torch.empty(B, hq * hd, dtype=x.dtype, device=x.device)
-    _native_call("dli_decode_attention_fused_win", _p(out), _p(src), splits, _p(positions),
+    if bias is None and qk_norm is None:
+        _native_call("dli_decode_attention_fused_win", _p(out), _p(src), splits, _p(positions),
+                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), _p(block_tables),
+                     block_tables.stride(0), _p(context_lens), B, hq, hkv, hd, k_cache.shape[2],
+                     scale, fmt, max(int(window), 0), _st())
+        return out
+    bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
+    _native_call("dli_decode_attention_fused_x", _p(out), _p(src), splits, _p(positions),
                  _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), _p(block_tables),
                  block_tables.stride(0), _p(context_lens), B, hq, hkv, hd, k_cache.shape[2],
-                 scale, fmt, max(int(window), 0), _st())
+                 scale, fmt, max(int(window), 0), _p(bias), _p(q_w), _p(k_w), eps, _st())
     return out
 
 
@@ -465,15 +505,26 @@ def bias_act_(x, bias, act: str = "none"):
 
 # ----------------------------------------------------------------------------- RoPE / KV cache
 def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
-                   use_rope: bool = True):
-    """In-place RoPE on q,k inside qkv + paged cache write. Returns views (q, k, v)."""
+                   use_rope: bool = True, bias=None, qk_norm=None):
+    """In-place RoPE on q,k inside qkv + paged cache write. Returns views (q, k, v).
+    ``bias`` [(hq+2hkv)*hd]: added to the rows first (Qwen2's QKV bias; rows that come from
+    ``linear(x, w, bias)`` already hold it). ``qk_norm`` = (q_w [hd], k_w [hd], eps): every q
+    and k head is RMS-normalised over its hd dims before the rotation (Qwen3); v is not.
+    Each step rounds to bf16: bias, norm, rotation."""
     if not _use_native(qkv):
         return R.rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv,
-                                hd, use_rope)
+                                hd, use_rope, bias=bias, qk_norm=qk_norm)
     T = qkv.shape[0]
     bs = k_cache.shape[2] if k_cache is not None else 16
-    _native_call("dli_rope_cache", _p(qkv), qkv.stride(0), _p(positions), _p(slot_mapping),
-                 _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs, int(use_rope), _st())
+    if bias is None and qk_norm is None:
+        _native_call("dli_rope_cache", _p(qkv), qkv.stride(0), _p(positions),
+                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs,
+                     int(use_rope), _st())
+        return R.split_qkv(qkv, hq, hkv, hd)
+    bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, (hq + 2 * hkv) * hd, hd)
+    _native_call("dli_rope_cache_x", _p(qkv), qkv.stride(0), _p(positions), _p(slot_mapping),
+                 _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs, int(use_rope),
+                 _p(bias), _p(q_w), _p(k_w), eps, _st())
     return R.split_qkv(qkv, hq, hkv, hd)
 
 

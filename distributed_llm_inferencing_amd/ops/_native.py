@@ -67,6 +67,11 @@ _SIGS = {
     "dli_decode_attention_fused": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, P],
     "dli_decode_attention_fused_win": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
                                        P],
+    # the three RoPE kernels with the Qwen extras: ..., qkv bias, q_norm w, k_norm w, eps, stream
+    "dli_rope_cache_x": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, P],
+    "dli_splitk_rope_cache_x": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, P],
+    "dli_decode_attention_fused_x": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
+                                     P, P, P, F, P],
     "dli_moe_route": [P, P, P, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

@@ -175,10 +175,19 @@ def write_kv(k: torch.Tensor, v: torch.Tensor, slot_mapping: torch.Tensor,
 
 
 def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache,
-                   hq: int, hkv: int, hd: int, use_rope: bool = True):
+                   hq: int, hkv: int, hd: int, use_rope: bool = True, bias=None, qk_norm=None):
     """Rotates q and k IN PLACE inside ``qkv`` and writes k/v to the paged cache.
-    Returns strided views (q [T,Hq,hd], k [T,Hkv,hd], v [T,Hkv,hd]) into ``qkv``."""
+    Returns strided views (q [T,Hq,hd], k [T,Hkv,hd], v [T,Hkv,hd]) into ``qkv``.
+    ``bias`` [(Hq+2Hkv)*hd] (Qwen2) is added to the rows first; ``qk_norm`` = (q_w [hd],
+    k_w [hd], eps) (Qwen3) then normalises every q and k head (``rmsnorm`` over its hd dims)
+    before the rotation; v gets the bias only. Each step rounds to ``qkv.dtype``."""
+    if bias is not None:
+        qkv.copy_((qkv.float() + bias.float()).to(qkv.dtype))
     q, k, v = split_qkv(qkv, hq, hkv, hd)
+    if qk_norm is not None:
+        q_w, k_w, eps = qk_norm
+        q.copy_(rmsnorm(q, q_w, eps))
+        k.copy_(rmsnorm(k, k_w, eps))
     if use_rope:
         q.copy_(apply_rope(q, positions, cos_sin))
         k.copy_(apply_rope(k, positions, cos_sin))

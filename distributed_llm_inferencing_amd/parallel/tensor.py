@@ -2,7 +2,8 @@
 layer-sharded pipeline — not the north star).
 
 Megatron-style split of every Llama layer over N ranks:
-    wqkv   column-parallel by heads (Hq/N query heads, Hkv/N kv heads per rank)
+    wqkv   column-parallel by heads (Hq/N query heads, Hkv/N kv heads per rank); a QKV bias
+           (bqkv, Qwen2) is sliced the same way, the per-head q_norm / k_norm are replicated
     wo     row-parallel (the rank's query-head columns) -> all-reduce(sum)
     w_gu   column-parallel in whole 32-row gate/up interleave groups (F/N features)
     w_down row-parallel -> all-reduce(sum)
@@ -40,6 +41,11 @@ def shard_param(name: str, t: torch.Tensor, cfg, rank: int, world: int) -> torch
         parts = [q[rank * qs:(rank + 1) * qs], k[rank * ks:(rank + 1) * ks],
                  v[rank * ks:(rank + 1) * ks]]
         return torch.cat([p.reshape(-1, t.shape[1]) for p in parts]).contiguous()
+    if name.endswith(".bqkv") and cfg.arch == "llama":       # Qwen2: sliced with wqkv's heads
+        qs, ks = hq // world * hd, hkv // world * hd
+        q, k, v = t[: hq * hd], t[hq * hd:(hq + hkv) * hd], t[(hq + hkv) * hd:]
+        return torch.cat([q[rank * qs:(rank + 1) * qs], k[rank * ks:(rank + 1) * ks],
+                          v[rank * ks:(rank + 1) * ks]]).contiguous()
     if name.endswith(".wo"):
         qs = hq // world
         return t[:, rank * qs * hd:(rank + 1) * qs * hd].contiguous()
