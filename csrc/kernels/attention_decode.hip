@@ -14,13 +14,19 @@
 //                                                in the prefill kernel)
 // With >1 split the per-split (m, l, O) go to a workspace merged by a second kernel.
 // decode_attn_fused_kernel (the decode-graph default) runs the same tile loop after a
-// prologue that replaces dli_splitk_rope_cache: the QKV GEMM's split-K slabs are reduced,
-// q/k rotated and k/v written to the paged cache inside the attention wave.
+// prologue that does the work of dli_splitk_rope_cache[_x] (qkv_rope.h) inside the attention
+// wave: the QKV GEMM's split-K slabs (or its bf16 rows) are reduced, biased and normalised
+// where the model asks for it, q/k rotated and k/v written to the paged cache.
+// Forms: decode_attn_kernel (a wave per item, one tile per round), decode_attn_wg_kernel (a
+// workgroup per item, small batches), decode_attn_pipe_kernel (software-pipelined, long
+// splits) and decode_attn_fused_kernel (a wave or a workgroup per item). They share the Q^T
+// fragment load, the S^T MFMAs, the online-softmax update and the finalize step below; the V
+// staging and the P.V reads are per kernel (the LDS layouts differ).
 //
 // Layouts: q rows of stride q_stride (the fused QKV buffer), k_cache and v_cache
 // [nblk,Hkv,bs,hd] (token-major: the per-step cache write is a contiguous row),
 // block_tables [B, max_blocks], out [B, Hq, hd].
-#include "common.h"
+#include "qkv_rope.h"
 #include <limits.h>
 #include <stdlib.h>
 
@@ -30,10 +36,6 @@
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-// The tile loop shared by the plain and the fused kernel: one wave = one (sequence, kv head,
-// split) item with its Q^T fragments already in registers.
-// The tile loop over tokens [s_begin, s_end): leaves the unnormalised O rows in o_acc, the
-// running max of head `col` in m_run and this lane's partial denominator in l_part.
 // The first 64-block window of the block-table row of tokens [s_begin, s_end), one block id
 // per lane (decode_attn_loop's bt_lane0): loaded by the caller so that the load can be
 // issued ahead of the prologue's cache write and its fence.
@@ -64,6 +66,128 @@ __device__ __forceinline__ void decode_wg_range(int lo, int ctx, int wv, int& s_
   s_end = min(ctx, s_begin + per * DEC_TILE);
 }
 
+// Q^T fragments (B operand) of item (b, kvh) from bf16 rows: head = col, dims 32kk + 8grp .. +7
+template <int HD>
+__device__ __forceinline__ void load_q_frags(const u16* __restrict__ q, int q_stride, int b,
+                                             int kvh, int G, int lane, bf16x8 (&qf)[HD / 32]) {
+  const int col = lane & 15, grp = lane >> 4;
+  const bool valid = col < G;
+  const u16* qp = q + (long)b * q_stride + (long)(kvh * G + (valid ? col : 0)) * HD;
+#pragma unroll
+  for (int kk = 0; kk < HD / 32; ++kk) {
+    uint4 v = valid ? *reinterpret_cast<const uint4*>(qp + kk * 32 + grp * 8)
+                    : make_uint4(0, 0, 0, 0);
+    qf[kk] = *reinterpret_cast<bf16x8*>(&v);
+  }
+}
+
+// S^T = K . Q^T for the two 16-token subtiles of a tile (kreg: the K rows as loaded); the
+// lane then holds S^T[tok = t0 + 16s + 4grp + r][head = col]
+template <int HD>
+__device__ __forceinline__ void decode_scores(uint4 (&kreg)[2][HD / 32],
+                                              const bf16x8 (&qf)[HD / 32], f32x4 (&s_acc)[2]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    s_acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < HD / 32; ++kk)
+      s_acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          *reinterpret_cast<bf16x8*>(&kreg[s][kk]), qf[kk], s_acc[s], 0, 0, 0);
+  }
+}
+
+// Online-softmax update of a tile at t0 (tokens >= s_end masked): new running max and partial
+// denominator, O rows rescaled, and the tile's P in p: P[head=col][k = 8grp + j] in the
+// permuted token order pi(grp, j) = 16(j>>2) + 4grp + (j&3). HW_EXP2: v_exp_f32 as it is (the
+// pipelined kernel) instead of exp2f.
+template <int HD, bool HW_EXP2>
+__device__ __forceinline__ void decode_softmax_update(const f32x4 (&s_acc)[2], int t0,
+                                                      int s_end, int grp, float scale_log2,
+                                                      float& m_run, float& l_part,
+                                                      f32x4 (&o_acc)[HD / 16], float (&p)[8]) {
+  auto ex2 = [](float x) { return HW_EXP2 ? __builtin_amdgcn_exp2f(x) : exp2f(x); };
+  float tmax = -INFINITY;
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int tok = t0 + 16 * s + 4 * grp + r;
+      const float v = tok < s_end ? s_acc[s][r] * scale_log2 : -INFINITY;
+      p[s * 4 + r] = v;
+      tmax = fmaxf(tmax, v);
+    }
+  tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+  tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+  const float m_new = fmaxf(m_run, tmax);
+  const float alpha = ex2(m_run - m_new);                      // m_run=-inf -> 0
+  m_run = m_new;
+  float psum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { p[j] = ex2(p[j] - m_new); psum += p[j]; }
+  l_part = l_part * alpha + psum;
+  // rescale O rows (heads 4grp + r) by their head's alpha (held by lane 4grp + r)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float a = __shfl(alpha, 4 * grp + r, 64);
+#pragma unroll
+    for (int i = 0; i < HD / 16; ++i) o_acc[i][r] *= a;
+  }
+}
+
+// P as the A operand of P . V (the loop kernels stage their V tile between the update and this)
+__device__ __forceinline__ bf16x8 decode_pack_p(const float (&p)[8]) {
+  bf16x8 pa;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pa[j] = (__bf16)p[j];
+  return pa;
+}
+
+// denominator of head `col` over the 4 lane groups
+__device__ __forceinline__ float decode_l_total(float l_part) {
+  const float l_tot = l_part + __shfl_xor(l_part, 16, 64);
+  return l_tot + __shfl_xor(l_tot, 32, 64);
+}
+
+// Finalize an item: rows 4grp + r of O over their denominators to `out` (one split) or,
+// with the (m, l) of each head, to the split workspace
+template <int HD>
+__device__ __forceinline__ void decode_finalize(const f32x4 (&o_acc)[HD / 16], float m_run,
+                                                float l_part, int lane, int b, int kvh,
+                                                int split, int G, int hq, int num_splits,
+                                                u16* __restrict__ out, float* __restrict__ ws_o,
+                                                float* __restrict__ ws_ml) {
+  constexpr int DB = HD / 16;
+  const int col = lane & 15, grp = lane >> 4;
+  const float l_tot = decode_l_total(l_part);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int h = 4 * grp + r;
+    const float lr = __shfl(l_tot, h, 64);
+    const float mr = __shfl(m_run, h, 64);
+    if (h >= G) continue;
+    const int qh = kvh * G + h;
+    const float inv = lr > 0.f ? 1.f / lr : 0.f;
+    if (num_splits == 1) {
+      u16* op = out + ((long)b * hq + qh) * HD;
+#pragma unroll
+      for (int i = 0; i < DB; ++i) op[16 * i + col] = f2bf(o_acc[i][r] * inv);
+    } else {
+      const long base = ((long)b * hq + qh) * num_splits + split;
+      float* wo = ws_o + base * HD;
+#pragma unroll
+      for (int i = 0; i < DB; ++i) wo[16 * i + col] = o_acc[i][r] * inv;
+      if (col == 0) {
+        ws_ml[base * 2] = lr > 0.f ? mr : -INFINITY;
+        ws_ml[base * 2 + 1] = lr;
+      }
+    }
+  }
+}
+
+// The tile loop of the one-tile-per-round kernels: one wave = one (sequence, kv head, split)
+// item with its Q^T fragments already in registers. Over tokens [s_begin, s_end) it leaves
+// the unnormalised O rows in o_acc, the running max of head `col` in m_run and this lane's
+// partial denominator in l_part.
 template <int HD>
 __device__ __forceinline__ void decode_attn_loop(
     const bf16x8 (&qf)[HD / 32], u16* vt, int lane, int b, int kvh, int s_begin, int s_end,
@@ -114,55 +238,17 @@ __device__ __forceinline__ void decode_attn_loop(
       vreg[m] = *reinterpret_cast<const uint4*>(
           v_cache + ((long)blk * hkv + kvh) * kv_head_stride + (long)off * HD + c * 8);
     }
-    // ---- S^T = K . Q^T for the two 16-token subtiles
     f32x4 s_acc[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      s_acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk)
-        s_acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            *reinterpret_cast<bf16x8*>(&kreg[s][kk]), qf[kk], s_acc[s], 0, 0, 0);
-    }
-    // lane holds S^T[tok = t0 + 16s + 4grp + r][head = col]
+    decode_scores<HD>(kreg, qf, s_acc);
     float p[8];
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int tok = t0 + 16 * s + 4 * grp + r;
-        const float v = tok < s_end ? s_acc[s][r] * scale_log2 : -INFINITY;
-        p[s * 4 + r] = v;
-        tmax = fmaxf(tmax, v);
-      }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = exp2f(m_run - m_new);                  // m_run=-inf -> 0
-    m_run = m_new;
-    float psum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { p[j] = exp2f(p[j] - m_new); psum += p[j]; }
-    l_part = l_part * alpha + psum;
-    // rescale O rows (heads 4grp + r) by their head's alpha (held by lane 4grp + r)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float a = __shfl(alpha, 4 * grp + r, 64);
-#pragma unroll
-      for (int i = 0; i < DB; ++i) o_acc[i][r] *= a;
-    }
+    decode_softmax_update<HD, false>(s_acc, t0, s_end, grp, scale_log2, m_run, l_part, o_acc, p);
     // stage the V tile in this wave's LDS rows (previous tile's reads retired below)
 #pragma unroll
     for (int m = 0; m < DB; ++m) {
       const int piece = lane + 64 * m, r = piece / VCH, c = piece % VCH;
       *reinterpret_cast<uint4*>(vt + r * VROW + c * 8) = vreg[m];
     }
-    // A operand: P[head=col][k = 8grp + j] in the permuted token order
-    // pi(grp, j) = 16(j>>2) + 4grp + (j&3)
-    bf16x8 pa;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pa[j] = (__bf16)p[j];
+    const bf16x8 pa = decode_pack_p(p);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // V tile writes landed (same wave)
     // B operand: rows (tokens) 4grp+q and 16+4grp+q, columns 16i + 4p, transposed by
     // ds_read_b64_tr_b16 (lane 4q+p of each 16-lane group names row q, columns 4p..4p+3)
@@ -190,17 +276,18 @@ __device__ __forceinline__ void decode_attn_core(
     const u16* __restrict__ v_cache, const int* __restrict__ block_tables, int max_blocks,
     int hq, int hkv, int block_size, float scale_log2, int num_splits,
     float* __restrict__ ws_o, float* __restrict__ ws_ml, int bt_lane0 = INT_MIN) {
-  constexpr int DB = HD / 16;
-  const int col = lane & 15, grp = lane >> 4;
-  f32x4 o_acc[DB];
+  f32x4 o_acc[HD / 16];
   float m_run, l_part;
   if (bt_lane0 == INT_MIN)
     bt_lane0 = decode_bt_window(block_tables, max_blocks, b, s_begin, s_end, block_size, lane);
   decode_attn_loop<HD>(qf, vt, lane, b, kvh, s_begin, s_end, k_cache, v_cache, block_tables,
                        max_blocks, hkv, block_size, scale_log2, bt_lane0, o_acc, m_run, l_part);
-  // ---- finalize: denominator of head `col`, then rows 4grp + r of O
-  float l_tot = l_part + __shfl_xor(l_part, 16, 64);
-  l_tot += __shfl_xor(l_tot, 32, 64);
+  // decode_finalize's text, kept as a copy: called as the helper, hipcc schedules the fused
+  // kernels' tile loop differently (first S^T MFMA ahead of the V loads), 2-5 % slower at
+  // batch 64 and contexts >= 100 (profiles/r9/README.md)
+  constexpr int DB = HD / 16;
+  const int col = lane & 15, grp = lane >> 4;
+  const float l_tot = decode_l_total(l_part);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int h = 4 * grp + r;
@@ -223,7 +310,8 @@ __device__ __forceinline__ void decode_attn_core(
         ws_ml[base * 2 + 1] = lr;
       }
     }
-  }}
+  }
+}
 
 // MINW = 4 waves per SIMD: <= 128 VGPRs, so every item of a 512-sequence batch (4096 waves)
 // is resident at once (measured 7 % faster than the 166-VGPR / 2-waves build at ctx 66)
@@ -252,7 +340,8 @@ __global__ void __launch_bounds__(256, MINW) decode_attn_kernel(
   const int s_begin = decode_win_lo(ctx, window) + split * split_tokens;
   const int s_end = min(ctx, s_begin + split_tokens);
 
-  // Q^T fragments (B operand): head = col, dims 32kk + 8grp .. +7
+  // load_q_frags' text, kept as a copy: through the helper hipcc waits on each fragment's load
+  // in turn, about 1 % at batch 64 with KV splits (profiles/r9/README.md)
   bf16x8 qf[KK];
   {
     const bool valid = col < G;
@@ -289,8 +378,7 @@ __device__ __forceinline__ void decode_attn_wg(
   decode_attn_loop<HD>(qf, vtile_all[wv], lane, b, kvh, s_begin, s_end, k_cache, v_cache,
                        block_tables, max_blocks, hkv, block_size, scale_log2, bt_lane0, o_acc,
                        m_run, l_part);
-  float l_tot = l_part + __shfl_xor(l_part, 16, 64);
-  l_tot += __shfl_xor(l_tot, 32, 64);
+  const float l_tot = decode_l_total(l_part);
   float* po = reinterpret_cast<float*>(vtile_all[wv]);
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -340,16 +428,7 @@ __global__ void __launch_bounds__(256) decode_attn_wg_kernel(
   const int col = lane & 15, grp = lane >> 4;
   const int G = hq / hkv;
   bf16x8 qf[KK];
-  {
-    const bool valid = col < G;
-    const u16* qp = q + (long)b * q_stride + (long)(kvh * G + (valid ? col : 0)) * HD;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      uint4 v = valid ? *reinterpret_cast<const uint4*>(qp + kk * 32 + grp * 8)
-                      : make_uint4(0, 0, 0, 0);
-      qf[kk] = *reinterpret_cast<bf16x8*>(&v);
-    }
-  }
+  load_q_frags<HD>(q, q_stride, b, kvh, G, lane, qf);
   int s_begin, s_end;
   const int ctx = context_lens[b];
   decode_wg_range<DEC_WAVES>(decode_win_lo(ctx, window), ctx, wv, s_begin, s_end);
@@ -397,7 +476,12 @@ struct DecodeQkvExtras {
 template <>
 struct DecodeQkvExtras<false> {};
 
-template <int SPL, int WPI, bool S16 = false, bool X = false>
+// The source kind is QkvSrc and the cache row kv_cache_row, as in qkv_rope.h; the Q slab sums
+// and the norm-and-round and rotate expressions stay written out here. hipcc contracts
+// x2 co + x1 si into either of its two fused forms per instantiation: the fp16-slab forms here
+// have fma(x1, si, x2 co), and with the sums read through Slab8 (this text otherwise
+// unchanged) they got fma(x2, co, x1 si), a few q elements per million (profiles/r9/README.md).
+template <QkvSrc SRC, int SPL, int WPI, bool X = false>
 __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     u16* __restrict__ out, const void* __restrict__ src, int N,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
@@ -413,9 +497,8 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
   if constexpr (X) {
     bias = ex.bias; q_norm_w = ex.q_norm_w; k_norm_w = ex.k_norm_w; qk_eps = ex.qk_eps;
   }
-  // SPL > 0: src = the QKV GEMM's fp32 split-K slabs [SPL, B, N]; SPL == 0: the bf16 QKV rows
-  // [B, N] of an unsplit GEMM (the same prologue minus the slab sum)
-  // S16: the slabs are fp16 x 1/16 (EPI_SLAB16), read as 16-bit words
+  // src: the QKV GEMM's SPL split-K slabs [SPL, B, N], fp32 or fp16 x 1/16 (EPI_SLAB16), or
+  // (ROWS, SPL 1) the bf16 QKV rows [B, N] of an unsplit GEMM: the same prologue minus the sum
   const float* ws = static_cast<const float*>(src);
   const u16* qkv = static_cast<const u16*>(src);
   const u16* ws16 = static_cast<const u16*>(src);
@@ -447,12 +530,12 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     for (int kp2 = 0; kp2 < KK / 2; ++kp2) {
       const int d1 = 32 * kp2 + 8 * grp;
       float x1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, x2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if constexpr (SPL == 0) {
+      if constexpr (SRC == QkvSrc::ROWS) {
         const u16* qr = qkv + rowoff + (long)(kvh * G + col) * HD;
         load8(qr + d1, x1);
         load8(qr + HALF + d1, x2);
       }
-      if constexpr (S16) {
+      if constexpr (SRC == QkvSrc::SLAB16) {
         const u16* qh = ws16 + rowoff + (long)(kvh * G + col) * HD;
         uint4 ua[SPL], uc[SPL];
 #pragma unroll
@@ -470,7 +553,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
         }
       }
 #pragma unroll
-      for (int s = 0; s < (S16 ? 0 : SPL); ++s) {
+      for (int s = 0; s < (SRC == QkvSrc::SLAB32 ? SPL : 0); ++s) {
         const float4* a = reinterpret_cast<const float4*>(qp + s * splitstride + d1);
         const float4* c = reinterpret_cast<const float4*>(qp + s * splitstride + HALF + d1);
         const float4 a0 = a[0], a1 = a[1], c0 = c[0], c1 = c[1];
@@ -551,7 +634,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
     const float* kp = ws + rowoff + (long)(hq + kvh) * HD;
     const float* vp = ws + rowoff + (long)(hq + hkv + kvh) * HD;
     float k1 = 0.f, k2 = 0.f, v1 = 0.f, v2 = 0.f;
-    if constexpr (S16) {
+    if constexpr (SRC == QkvSrc::SLAB16) {
       const u16* kh = ws16 + rowoff + (long)(hq + kvh) * HD;
       const u16* vh = ws16 + rowoff + (long)(hq + hkv + kvh) * HD;
 #pragma unroll
@@ -561,7 +644,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
         v1 += h2f(vh[s * splitstride + lane]) * SLAB16_UNSCALE;
         v2 += h2f(vh[s * splitstride + HALF + lane]) * SLAB16_UNSCALE;
       }
-    } else if constexpr (SPL > 0) {
+    } else if constexpr (SRC == QkvSrc::SLAB32) {
 #pragma unroll
       for (int s = 0; s < SPL; ++s) {
         k1 += kp[s * splitstride + lane];
@@ -592,8 +675,7 @@ __global__ void __launch_bounds__(256, 4) decode_attn_fused_kernel(
       }
     }
     const float co = cs[lane], si = cs[HALF + lane];
-    const int blk = slot / block_size, off = slot - blk * block_size;
-    const long dst = (((long)blk * hkv + kvh) * block_size + off) * HD;
+    const long dst = kv_cache_row(slot, block_size, hkv, kvh, HD);
     k_cache[dst + lane] = f2bf(k1 * co - k2 * si);
     k_cache[dst + HALF + lane] = f2bf(k2 * co + k1 * si);
     v_cache[dst + lane] = f2bf(v1);
@@ -656,15 +738,8 @@ __global__ void __launch_bounds__(256, 2) decode_attn_pipe_kernel(
     se = min(ctx, sb + split_tokens);
   };
   auto ntiles_of = [&](int sb, int se) { return se > sb ? (se - sb + DEC_TILE - 1) / DEC_TILE : 1; };
-  auto load_q = [&](int b, int kvh, bf16x8* dst) {
-    const bool valid = col < G;
-    const u16* qp = q + (long)b * q_stride + (long)(kvh * G + (valid ? col : 0)) * HD;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      uint4 v = valid ? *reinterpret_cast<const uint4*>(qp + kk * 32 + grp * 8)
-                      : make_uint4(0, 0, 0, 0);
-      dst[kk] = *reinterpret_cast<bf16x8*>(&v);
-    }
+  auto load_q = [&](int b, int kvh, bf16x8 (&dst)[KK]) {
+    load_q_frags<HD>(q, q_stride, b, kvh, G, lane, dst);
   };
   int pb, pkvh, psplit, psb, pse;
   geom(p_item, pb, pkvh, psplit, psb, pse);
@@ -735,31 +810,8 @@ __global__ void __launch_bounds__(256, 2) decode_attn_pipe_kernel(
   for (int i = 0; i < DB; ++i) o_acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   auto finalize = [&]() {
-    float l_tot = l_part + __shfl_xor(l_part, 16, 64);
-    l_tot += __shfl_xor(l_tot, 32, 64);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int h = 4 * grp + r;
-      const float lr = __shfl(l_tot, h, 64);
-      const float mr = __shfl(m_run, h, 64);
-      if (h >= G) continue;
-      const int qh = ckvh * G + h;
-      const float inv = lr > 0.f ? 1.f / lr : 0.f;
-      if (num_splits == 1) {
-        u16* op = out + ((long)cb * hq + qh) * HD;
-#pragma unroll
-        for (int i = 0; i < DB; ++i) op[16 * i + col] = f2bf(o_acc[i][r] * inv);
-      } else {
-        const long base = ((long)cb * hq + qh) * num_splits + csplit;
-        float* wo = ws_o + base * HD;
-#pragma unroll
-        for (int i = 0; i < DB; ++i) wo[16 * i + col] = o_acc[i][r] * inv;
-        if (col == 0) {
-          ws_ml[base * 2] = lr > 0.f ? mr : -INFINITY;
-          ws_ml[base * 2 + 1] = lr;
-        }
-      }
-    }
+    decode_finalize<HD>(o_acc, m_run, l_part, lane, cb, ckvh, csplit, G, hq, num_splits, out,
+                        ws_o, ws_ml);
   };
   // compute cursor's unit from K registers kr and V tile vbuf; `later` = the next unit's
   // loads were issued after this unit's V DMA (then vmcnt(16) retires exactly this tile:
@@ -769,43 +821,10 @@ __global__ void __launch_bounds__(256, 2) decode_attn_pipe_kernel(
     if (cse > csb) {
       const int t0 = csb + DEC_TILE * c_tile;
       f32x4 s_acc[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        s_acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk)
-          s_acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              *reinterpret_cast<bf16x8*>(&kr[s][kk]), qf[kk], s_acc[s], 0, 0, 0);
-      }
+      decode_scores<HD>(kr, qf, s_acc);
       float p[8];
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int tok = t0 + 16 * s + 4 * grp + r;
-          const float v = tok < cse ? s_acc[s][r] * scale_log2 : -INFINITY;
-          p[s * 4 + r] = v;
-          tmax = fmaxf(tmax, v);
-        }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float m_new = fmaxf(m_run, tmax);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);     // m_run=-inf -> 0
-      m_run = m_new;
-      float psum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { p[j] = __builtin_amdgcn_exp2f(p[j] - m_new); psum += p[j]; }
-      l_part = l_part * alpha + psum;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = __shfl(alpha, 4 * grp + r, 64);
-#pragma unroll
-        for (int i = 0; i < DB; ++i) o_acc[i][r] *= a;
-      }
-      bf16x8 pa;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pa[j] = (__bf16)p[j];
+      decode_softmax_update<HD, true>(s_acc, t0, cse, grp, scale_log2, m_run, l_part, o_acc, p);
+      const bf16x8 pa = decode_pack_p(p);
       if (later) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // this V tile landed
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const char* vt = vt_all[wv][vbuf];
@@ -950,17 +969,17 @@ extern "C" int dli_decode_attention_win(void* out, const void* q, int q_stride,
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
         block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window);
   } else {
-  dim3 grid((int)((items + DEC_WAVES - 1) / DEC_WAVES));
-  if (hd == 128)
-    decode_attn_kernel<128, 4><<<grid, 64 * DEC_WAVES, 0, st>>>(
-        (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
-        block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml, window);
-  else
-    decode_attn_kernel<64, 1><<<grid, 64 * DEC_WAVES, 0, st>>>(
-        (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
-        block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml, window);
+    dim3 grid((int)((items + DEC_WAVES - 1) / DEC_WAVES));
+    if (hd == 128)
+      decode_attn_kernel<128, 4><<<grid, 64 * DEC_WAVES, 0, st>>>(
+          (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
+          block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2,
+          num_splits, split_tokens, ws_o, ws_ml, window);
+    else
+      decode_attn_kernel<64, 1><<<grid, 64 * DEC_WAVES, 0, st>>>(
+          (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
+          block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2,
+          num_splits, split_tokens, ws_o, ws_ml, window);
   }
   if (num_splits > 1) {
     const long total = (long)B * hq * (hd / 8);
@@ -988,8 +1007,8 @@ extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, cons
 // with splits == 0 the bf16 QKV rows [B, (hq + 2 hkv) * 128] of an unsplit GEMM.
 // fmt: 0 = fp32 slabs (or the bf16 rows when splits == 0), 1 = fp16 x 1/16 slabs (EPI_SLAB16)
 // window > 0: sliding-window attention (decode_win_lo)
-// bias [N] / q_norm_w, k_norm_w [128] (the two together): bf16, 16-B aligned, or null;
-// all null = dli_decode_attention_fused_win
+// bias [N] / q_norm_w, k_norm_w [128]: see qkv_extras_ok; all null =
+// dli_decode_attention_fused_win
 extern "C" int dli_decode_attention_fused_x(void* out, const void* ws, int splits,
                                             const int* positions, const int* slot_mapping,
                                             const float* cos_sin, void* k_cache, void* v_cache,
@@ -1005,36 +1024,37 @@ extern "C" int dli_decode_attention_fused_x(void* out, const void* ws, int split
       (splits != 0 && splits != 2 && splits != 4) || fmt < 0 || fmt > 1 ||
       (fmt == 1 && splits == 0))
     return (int)hipErrorInvalidValue;
-  if ((q_norm_w == nullptr) != (k_norm_w == nullptr) ||
-      (((uintptr_t)bias | (uintptr_t)q_norm_w | (uintptr_t)k_norm_w) & 15))
-    return (int)hipErrorInvalidValue;
+  if (!qkv_extras_ok(bias, q_norm_w, k_norm_w, hd)) return (int)hipErrorInvalidValue;
   const bool extras = bias != nullptr || q_norm_w != nullptr;
   const int N = (hq + 2 * hkv) * hd;
   const float scale_log2 = scale * 1.4426950408889634f;
   const long items = (long)B * hkv;
   const bool per_wg = wg_form(items);
   dim3 grid((int)(per_wg ? items : (items + DEC_WAVES - 1) / DEC_WAVES));
-#define DLI_DAFX(S, W, F, X, ...) decode_attn_fused_kernel<S, W, F, X>                        \
+#define DLI_DAFX(SRC, S, W, X, ...) decode_attn_fused_kernel<QkvSrc::SRC, S, W, X>            \
       <<<grid, 64 * DEC_WAVES, 0, st>>>(                                                     \
       (u16*)out, ws, N, positions, slot_mapping, cos_sin, (u16*)k_cache, (u16*)v_cache,      \
       block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, window,    \
       DecodeQkvExtras<X>{__VA_ARGS__})
-#define DLI_DAF(S, W, F)                                                                      \
-  do {                                                                                        \
-    if (extras)                                                                               \
-      DLI_DAFX(S, W, F, true, (const u16*)bias, (const u16*)q_norm_w, (const u16*)k_norm_w,   \
-               qk_eps);                                                                       \
-    else                                                                                      \
-      DLI_DAFX(S, W, F, false);                                                               \
-  } while (0)
-  if (per_wg) {
-    if (splits == 0) DLI_DAF(0, DEC_WAVES, false);
-    else if (splits == 2) { if (fmt) DLI_DAF(2, DEC_WAVES, true); else DLI_DAF(2, DEC_WAVES, false); }
-    else { if (fmt) DLI_DAF(4, DEC_WAVES, true); else DLI_DAF(4, DEC_WAVES, false); }
-  } else {
-    if (splits == 0) DLI_DAF(0, 1, false);
-    else if (splits == 2) { if (fmt) DLI_DAF(2, 1, true); else DLI_DAF(2, 1, false); }
-    else { if (fmt) DLI_DAF(4, 1, true); else DLI_DAF(4, 1, false); }
+  // one case per (source, slab count) x (a wave, a workgroup per item)
+#define DLI_DAF(SRC, S)                                                                       \
+  case 8 * S + 2 * (int)QkvSrc::SRC:                                                          \
+    if (extras) DLI_DAFX(SRC, S, 1, true, (const u16*)bias, (const u16*)q_norm_w,             \
+                         (const u16*)k_norm_w, qk_eps);                                       \
+    else DLI_DAFX(SRC, S, 1, false);                                                          \
+    break;                                                                                    \
+  case 8 * S + 2 * (int)QkvSrc::SRC + 1:                                                      \
+    if (extras) DLI_DAFX(SRC, S, DEC_WAVES, true, (const u16*)bias, (const u16*)q_norm_w,     \
+                         (const u16*)k_norm_w, qk_eps);                                       \
+    else DLI_DAFX(SRC, S, DEC_WAVES, false);                                                  \
+    break
+  const QkvSrc srck = splits == 0 ? QkvSrc::ROWS : fmt ? QkvSrc::SLAB16 : QkvSrc::SLAB32;
+  switch (8 * (splits ? splits : 1) + 2 * (int)srck + (per_wg ? 1 : 0)) {
+    DLI_DAF(ROWS, 1);
+    DLI_DAF(SLAB32, 2);
+    DLI_DAF(SLAB32, 4);
+    DLI_DAF(SLAB16, 2);
+    DLI_DAF(SLAB16, 4);
   }
 #undef DLI_DAF
 #undef DLI_DAFX

@@ -138,3 +138,96 @@ __device__ __forceinline__ void unpack8h(const uint4 u, float* f) {
   }
 }
 
+// What a consumer of a GEMM output reads: the bf16 rows themselves, or the split-K partial
+// slabs of a GEMM called with C == nullptr, fp32 or fp16 x 1/16 (fmt 1 of the launchers).
+enum class QkvSrc { ROWS, SLAB32, SLAB16 };
+constexpr int qkv_src_bytes(QkvSrc s) { return s == QkvSrc::SLAB32 ? 4 : 2; }
+
+// Reader of 8 consecutive columns of SPL slabs (ROWS: of the one row), in two phases because
+// the callers put their other loads (residual, norm weight, router rows) between them:
+// issue() starts every load (SPL x 16 B, fp32 slabs 2 x 16 B each), sum() gives the fp32 sum
+// in slab order 0..S-1, starting from +0 as every consumer of the slabs must (a sum of -0
+// partials is +0). `off` and `stride` (slab to slab) count elements of the source.
+// SPL == 0: `splits` slabs in a runtime loop, nothing in flight ahead of the first add.
+template <QkvSrc SRC, int SPL>
+struct Slab8 {
+  static constexpr int W = SRC == QkvSrc::SLAB32 ? 2 : 1;      // 16-B words per slab
+  uint4 u[SPL][W];
+  __device__ __forceinline__ void load(int s, const void* src, long off, long stride) {
+    static_assert(SRC != QkvSrc::ROWS || SPL == 1, "a row is one source");
+    const char* p = static_cast<const char*>(src) + (s * stride + off) * qkv_src_bytes(SRC);
+#pragma unroll
+    for (int i = 0; i < W; ++i) u[s][i] = reinterpret_cast<const uint4*>(p)[i];
+  }
+  // (the count is the template's; the last argument exists so that callers of this form and
+  // of the runtime-loop form read alike, and a value other than SPL is not looked at)
+  __device__ __forceinline__ void issue(const void* src, long off, long stride, int = SPL) {
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) load(s, src, off, stride);
+  }
+  __device__ __forceinline__ void sum(float* x) const {
+    if constexpr (SRC == QkvSrc::ROWS) {
+      unpack8bf(u[0][0], x);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = 0.f;
+#pragma unroll
+      for (int s = 0; s < SPL; ++s) add8(x, u[s]);
+    }
+  }
+  static __device__ __forceinline__ void add8(float* x, const uint4* v) {
+    static_assert(SRC != QkvSrc::ROWS, "a row is read, not summed");
+    float f[8];
+    if constexpr (SRC == QkvSrc::SLAB16) {
+      unpack8h(v[0], f);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        f[4 * i] = __uint_as_float(v[i].x); f[4 * i + 1] = __uint_as_float(v[i].y);
+        f[4 * i + 2] = __uint_as_float(v[i].z); f[4 * i + 3] = __uint_as_float(v[i].w);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] += f[j];
+  }
+};
+template <QkvSrc SRC>
+struct Slab8<SRC, 0> {
+  const char* p;
+  long step;
+  int n;
+  __device__ __forceinline__ void issue(const void* src, long off, long stride, int splits) {
+    p = static_cast<const char*>(src) + off * qkv_src_bytes(SRC);
+    step = stride * qkv_src_bytes(SRC);
+    n = splits;
+  }
+  __device__ __forceinline__ void sum(float* x) const {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = 0.f;
+    for (int s = 0; s < n; ++s) {
+      uint4 v[Slab8<SRC, 1>::W];
+#pragma unroll
+      for (int i = 0; i < Slab8<SRC, 1>::W; ++i)
+        v[i] = reinterpret_cast<const uint4*>(p + s * step)[i];
+      Slab8<SRC, 1>::add8(x, v);
+    }
+  }
+};
+
+// issue() of a lane's two column groups (a head's RoPE partners), slab by slab: the order
+// under which the 8-slab forms keep the parent's register count (profiles/r9/README.md)
+template <QkvSrc SRC, int SPL>
+__device__ __forceinline__ void slab8_issue2(Slab8<SRC, SPL>& a, Slab8<SRC, SPL>& b,
+                                             const void* src, long off_a, long off_b,
+                                             long stride, int splits = SPL) {
+  if constexpr (SPL > 0) {
+#pragma unroll
+    for (int s = 0; s < SPL; ++s) {
+      a.load(s, src, off_a, stride);
+      b.load(s, src, off_b, stride);
+    }
+  } else {
+    a.issue(src, off_a, stride, splits);
+    b.issue(src, off_b, stride, splits);
+  }
+}

@@ -10,13 +10,13 @@
 // EPI_SLAB16 epilogue of the MFMA families) fp16 scaled by 1/16. The sum is fp32 in slab
 // order 0..S-1 and rounded to bf16 before the residual add / rotation, exactly as the bf16
 // GEMM output would be.
-#include "common.h"
+#include "qkv_rope.h"
 #include <stdlib.h>
 
 // SPL > 0: the split count is a compile-time constant, so every partial of a thread is
 // loaded before the first add (SPL x VPT x 2 16-B loads in flight per lane instead of 2 x VPT);
-// SPL == 0 reads `splits` partials in a runtime loop.
-template <int VPT, int SPL, bool S16 = false>
+// SPL == 0 reads `splits` partials in a runtime loop (Slab8).
+template <int VPT, int SPL, QkvSrc SRC = QkvSrc::SLAB32>
 __global__ void __launch_bounds__(512) splitk_add_rmsnorm_kernel(
     u16* __restrict__ out, u16* __restrict__ residual, const float* __restrict__ ws, int splits,
     int M, int N, const u16* __restrict__ w, float eps) {
@@ -29,41 +29,10 @@ __global__ void __launch_bounds__(512) splitk_add_rmsnorm_kernel(
   for (int i = 0; i < VPT; ++i) {
     const int vi = threadIdx.x + i * blockDim.x;
     if (vi < nvec) {
-      float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if constexpr (S16) {                        // fp16 slabs: one 16-B load per slab
-        const u16* ws16 = reinterpret_cast<const u16*>(ws);
-        uint4 pu[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s)
-          pu[s] = *reinterpret_cast<const uint4*>(ws16 + ((long)s * M + row) * N + vi * 8);
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-          float f[8];
-          unpack8h(pu[s], f);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[j] += f[j];
-        }
-      } else if constexpr (SPL > 0) {
-        float4 pa[SPL], pb[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-          const float4* p = reinterpret_cast<const float4*>(ws + ((long)s * M + row) * N + vi * 8);
-          pa[s] = p[0];
-          pb[s] = p[1];
-        }
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-          acc[0] += pa[s].x; acc[1] += pa[s].y; acc[2] += pa[s].z; acc[3] += pa[s].w;
-          acc[4] += pb[s].x; acc[5] += pb[s].y; acc[6] += pb[s].z; acc[7] += pb[s].w;
-        }
-      } else {
-        for (int s = 0; s < splits; ++s) {
-          const float4* p = reinterpret_cast<const float4*>(ws + ((long)s * M + row) * N + vi * 8);
-          const float4 a = p[0], b = p[1];
-          acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-          acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
-        }
-      }
+      Slab8<SRC, SPL> rd;
+      rd.issue(ws, (long)row * N + vi * 8, (long)M * N, splits);
+      float acc[8];
+      rd.sum(acc);
       float r[8];
       u16* rp = residual + (long)row * N + vi * 8;
       load8(rp, r);
@@ -94,9 +63,9 @@ static int launch_add_rmsnorm(u16* o, u16* r, const float* ws, int splits, int M
                               const u16* wp, float eps, int threads, int fmt, hipStream_t st) {
   if (fmt == 1) {                                  // fp16 slabs: the planner's 2 / 4 / 8 splits
     switch (splits) {
-      case 2: splitk_add_rmsnorm_kernel<VPT, 2, true><<<M, threads, 0, st>>>(o, r, ws, 2, M, N, wp, eps); break;
-      case 4: splitk_add_rmsnorm_kernel<VPT, 4, true><<<M, threads, 0, st>>>(o, r, ws, 4, M, N, wp, eps); break;
-      case 8: splitk_add_rmsnorm_kernel<VPT, 8, true><<<M, threads, 0, st>>>(o, r, ws, 8, M, N, wp, eps); break;
+      case 2: splitk_add_rmsnorm_kernel<VPT, 2, QkvSrc::SLAB16><<<M, threads, 0, st>>>(o, r, ws, 2, M, N, wp, eps); break;
+      case 4: splitk_add_rmsnorm_kernel<VPT, 4, QkvSrc::SLAB16><<<M, threads, 0, st>>>(o, r, ws, 4, M, N, wp, eps); break;
+      case 8: splitk_add_rmsnorm_kernel<VPT, 8, QkvSrc::SLAB16><<<M, threads, 0, st>>>(o, r, ws, 8, M, N, wp, eps); break;
       default: return (int)hipErrorInvalidValue;
     }
     DLI_RETURN_LAUNCH();
@@ -130,25 +99,17 @@ __global__ void __launch_bounds__(512) splitk_add_rmsnorm_route_kernel(
   const int row = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
   const long off = (long)row * N + tid * 8;
-  uint4 pu[SPL], rv, wvv, ru[EM];
-#pragma unroll
-  for (int s = 0; s < SPL; ++s)
-    pu[s] = *reinterpret_cast<const uint4*>(ws16 + (long)s * M * N + off);
+  Slab8<QkvSrc::SLAB16, SPL> rd;
+  uint4 rv, wvv, ru[EM];
+  rd.issue(ws16, off, (long)M * N);
   rv = *reinterpret_cast<const uint4*>(residual + off);
   wvv = *reinterpret_cast<const uint4*>(w + tid * 8);
 #pragma unroll
   for (int e = 0; e < EM; ++e)
     ru[e] = *reinterpret_cast<const uint4*>(wr + (long)min(e, E - 1) * N + tid * 8);
   __builtin_amdgcn_sched_barrier(0);
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int s = 0; s < SPL; ++s) {
-    float f[8];
-    unpack8h(pu[s], f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += f[j];
-  }
-  float r[8], v[8], ss = 0.f;
+  float acc[8], r[8], v[8], ss = 0.f;
+  rd.sum(acc);
   unpack8bf(rv, r);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -234,159 +195,33 @@ extern "C" int dli_splitk_add_rmsnorm(void* out, void* residual, const float* ws
   }
 }
 
-// one lane: 8 dims of the first half of a head + the matching 8 of the second half. SPL > 0:
-// compile-time split count, every partial's loads issued before the first add (and the
-// position / cos-sin loads ahead of them); SPL == 0: runtime loop.
-//
-// X (dli_splitk_rope_cache_x, the Qwen families): bias [N] (or null) is added to the fp32
-// slab sum before the one rounding that stands for the GEMM output; then every q and k head
-// is RMS-normalised over its hd dims with q_norm_w / k_norm_w [hd] (or null) and rounded to
-// bf16 before the rotation (v: bias only). The hd / 16 lanes of a head are consecutive,
-// aligned in the wave and leave together at the gid guard: log2(hd / 16) xor-shuffles.
-template <int SPL, bool S16, bool X>
-__device__ __forceinline__ void splitk_rope_cache_body(
-    u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
-    const int* __restrict__ positions, const int* __restrict__ slot_mapping,
-    const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
-    int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
-    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps) {
-  const int lanes_per_head = hd >> 4;
-  const int heads = hq + 2 * hkv;
-  const long total = (long)T * heads * lanes_per_head;
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= total) return;
-  const int c = (int)(gid % lanes_per_head);
-  const long th = gid / lanes_per_head;
-  const int h = (int)(th % heads);
-  const int t = (int)(th / heads);
-  const int half = hd >> 1, d0 = c * 8;
-  const long col1 = (long)h * hd + d0, col2 = col1 + half;
-  const bool is_q = h < hq, is_k = !is_q && h < hq + hkv;
-  const bool rope = use_rope && (is_q || is_k);
-  const int pos = rope ? positions[t] : 0;
-  float x1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, x2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto add4 = [](float* x, const float4& a, const float4& b) {
-    x[0] += a.x; x[1] += a.y; x[2] += a.z; x[3] += a.w;
-    x[4] += b.x; x[5] += b.y; x[6] += b.z; x[7] += b.w;
-  };
-  if constexpr (S16) {                             // fp16 slabs: one 16-B load per half-row
-    const u16* ws16 = reinterpret_cast<const u16*>(ws);
-    uint4 pu[SPL], pv[SPL];
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-      const u16* base = ws16 + ((long)s * T + t) * N;
-      pu[s] = *reinterpret_cast<const uint4*>(base + col1);
-      pv[s] = *reinterpret_cast<const uint4*>(base + col2);
-    }
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-      float f1[8], f2[8];
-      unpack8h(pu[s], f1);
-      unpack8h(pv[s], f2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { x1[j] += f1[j]; x2[j] += f2[j]; }
-    }
-  } else if constexpr (SPL > 0) {
-    float4 pa[SPL], pb[SPL], pe[SPL], pf[SPL];
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-      const float* base = ws + ((long)s * T + t) * N;
-      const float4* p1 = reinterpret_cast<const float4*>(base + col1);
-      const float4* p2 = reinterpret_cast<const float4*>(base + col2);
-      pa[s] = p1[0]; pb[s] = p1[1]; pe[s] = p2[0]; pf[s] = p2[1];
-    }
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) { add4(x1, pa[s], pb[s]); add4(x2, pe[s], pf[s]); }
-  } else {
-    for (int s = 0; s < splits; ++s) {
-      const float* base = ws + ((long)s * T + t) * N;
-      const float4* p1 = reinterpret_cast<const float4*>(base + col1);
-      const float4* p2 = reinterpret_cast<const float4*>(base + col2);
-      add4(x1, p1[0], p1[1]);
-      add4(x2, p2[0], p2[1]);
-    }
-  }
-  if constexpr (X) {
-    if (bias != nullptr) {
-      float b1[8], b2[8];
-      load8(bias + col1, b1);
-      load8(bias + col2, b2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { x1[j] += b1[j]; x2[j] += b2[j]; }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { x1[j] = bf2f(f2bf(x1[j])); x2[j] = bf2f(f2bf(x2[j])); }
-  if constexpr (X) {
-    if (q_norm_w != nullptr) {
-      float ss = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ss += x1[j] * x1[j] + x2[j] * x2[j];
-      // every lane of the wave that passed the guard shuffles (v heads too, unused there)
-      for (int o = 1; o < lanes_per_head; o <<= 1) ss += __shfl_xor(ss, o, 64);
-      if (is_q || is_k) {
-        const float rstd = rsqrtf(ss / hd + qk_eps);
-        const u16* wn = is_q ? q_norm_w : k_norm_w;
-        float w1[8], w2[8];
-        load8(wn + d0, w1);
-        load8(wn + half + d0, w2);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          x1[j] = bf2f(f2bf(x1[j] * rstd * w1[j]));
-          x2[j] = bf2f(f2bf(x2[j] * rstd * w2[j]));
-        }
-      }
-    }
-  }
-  if (rope) {
-    const float* cs = cos_sin + (long)pos * hd;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float co = cs[d0 + j], si = cs[half + d0 + j];
-      const float o1 = x1[j] * co - x2[j] * si, o2 = x2[j] * co + x1[j] * si;
-      x1[j] = bf2f(f2bf(o1));
-      x2[j] = bf2f(f2bf(o2));
-    }
-  }
-  u16* row = qkv + (long)t * N;
-  store8(row + col1, x1);
-  store8(row + col2, x2);
-  if (is_q || k_cache == nullptr) return;
-  const int slot = slot_mapping[t];
-  if (slot < 0) return;
-  const int blk = slot / block_size, off = slot - blk * block_size;
-  // K and V share the token-major [blk, head, off, hd] layout: whole-row 16-B stores
-  u16* dst = is_k ? k_cache + (((long)blk * hkv + (h - hq)) * block_size + off) * hd
-                  : v_cache + (((long)blk * hkv + (h - hq - hkv)) * block_size + off) * hd;
-  store8(dst + d0, x1);
-  store8(dst + half + d0, x2);
-}
-
-template <int SPL, bool S16 = false>
+// qkv_rope_cache_body (qkv_rope.h) on the slabs. SPL > 0: compile-time split count, every
+// partial's loads issued before the first add (and the position load ahead of them);
+// SPL == 0: runtime loop.
+template <int SPL, QkvSrc SRC>
 __global__ void __launch_bounds__(256) splitk_rope_cache_kernel(
     u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
     const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
     int hq, int hkv, int hd, int block_size, int use_rope) {
-  splitk_rope_cache_body<SPL, S16, false>(qkv, ws, splits, T, N, positions, slot_mapping,
-                                          cos_sin, k_cache, v_cache, hq, hkv, hd, block_size,
-                                          use_rope, nullptr, nullptr, nullptr, 0.f);
+  qkv_rope_cache_body<SRC, SPL, false>(qkv, N, ws, splits, positions, slot_mapping, cos_sin,
+                                       k_cache, v_cache, T, hq, hkv, hd, block_size, use_rope,
+                                       nullptr, nullptr, nullptr, 0.f);
 }
 
-template <int SPL, bool S16 = false>
+template <int SPL, QkvSrc SRC>
 __global__ void __launch_bounds__(256) splitk_rope_cache_x_kernel(
     u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
     const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
     int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
     const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps) {
-  splitk_rope_cache_body<SPL, S16, true>(qkv, ws, splits, T, N, positions, slot_mapping,
-                                         cos_sin, k_cache, v_cache, hq, hkv, hd, block_size,
-                                         use_rope, bias, q_norm_w, k_norm_w, qk_eps);
+  qkv_rope_cache_body<SRC, SPL, true>(qkv, N, ws, splits, positions, slot_mapping, cos_sin,
+                                      k_cache, v_cache, T, hq, hkv, hd, block_size, use_rope,
+                                      bias, q_norm_w, k_norm_w, qk_eps);
 }
 
-// bias / q_norm_w / k_norm_w: bf16, 16-B aligned, or null (the two norm weights together);
-// all null = dli_splitk_rope_cache
+// bias / q_norm_w / k_norm_w: see qkv_extras_ok; all null = dli_splitk_rope_cache
 extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, int T, int N,
                                        const int* positions, const int* slot_mapping,
                                        const float* cos_sin, void* k_cache, void* v_cache,
@@ -400,11 +235,7 @@ extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, i
   const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
   const int blocks = (int)((total + 255) / 256);
   const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
-  const int lph = hd / 16;                       // the head's lanes must be a shuffle group
-  if (extras && ((q_norm_w == nullptr) != (k_norm_w == nullptr) ||
-                 (q_norm_w != nullptr && ((lph & (lph - 1)) || lph > 64)) ||
-                 (((uintptr_t)bias | (uintptr_t)q_norm_w | (uintptr_t)k_norm_w) & 15)))
-    return (int)hipErrorInvalidValue;
+  if (!qkv_extras_ok(bias, q_norm_w, k_norm_w, hd)) return (int)hipErrorInvalidValue;
 #define DLI_SRC(S, F)                                                                       \
   do {                                                                                      \
     if (extras)                                                                             \
@@ -419,15 +250,15 @@ extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, i
   } while (0)
   if (fmt == 1) {
     switch (splits) {
-      case 2: DLI_SRC(2, true); break;
-      case 4: DLI_SRC(4, true); break;
-      default: DLI_SRC(8, true);
+      case 2: DLI_SRC(2, QkvSrc::SLAB16); break;
+      case 4: DLI_SRC(4, QkvSrc::SLAB16); break;
+      default: DLI_SRC(8, QkvSrc::SLAB16);
     }
   } else {
     switch (splits) {
-      case 2: DLI_SRC(2, false); break;
-      case 4: DLI_SRC(4, false); break;
-      default: DLI_SRC(0, false);
+      case 2: DLI_SRC(2, QkvSrc::SLAB32); break;
+      case 4: DLI_SRC(4, QkvSrc::SLAB32); break;
+      default: DLI_SRC(0, QkvSrc::SLAB32);
     }
   }
 #undef DLI_SRC

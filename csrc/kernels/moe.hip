@@ -231,6 +231,27 @@ extern "C" int dli_moe_combine(void* out, const void* y, const float* w, const i
   DLI_RETURN_LAUNCH();
 }
 
+// acc = sum_j w_j bf16(sum_s P_s[pos_j]) over token t's k picks, columns 8c .. 8c+7 (fp16
+// slabs, Slab8); a pick with pos < 0 (dropped) adds nothing
+template <int S>
+__device__ __forceinline__ void moe_combine_slab_picks(
+    const u16* __restrict__ ws, long slab_stride, const float* __restrict__ w,
+    const int* __restrict__ pos, int t, int k, int dim, int c, float* acc) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+  for (int j = 0; j < k; ++j) {
+    const int p = pos[t * k + j];
+    if (p < 0) continue;
+    Slab8<QkvSrc::SLAB16, S> rd;
+    rd.issue(ws, (long)p * dim + c * 8, slab_stride);
+    float v[8];
+    rd.sum(v);
+    const float ww = w[t * k + j];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] += ww * bf2f(f2bf(v[q]));
+  }
+}
+
 // The combine fused with the down projection's split-K reduce: the grouped down GEMM leaves
 // S fp16 x 1/16 partial slabs [S, rows, dim] (EPI_SLAB16, permuted rows) instead of a bf16 y;
 // each (token, pick) row is summed over the slabs in slab order, rounded to bf16 exactly as
@@ -244,26 +265,8 @@ __global__ void __launch_bounds__(256) moe_combine_slabs_kernel(
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= (long)T * chunks) return;
   const int t = (int)(gid / chunks), c = (int)(gid % chunks);
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int j = 0; j < k; ++j) {
-    const int p = pos[t * k + j];
-    if (p < 0) continue;
-    uint4 u[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-      u[s] = *reinterpret_cast<const uint4*>(ws + s * slab_stride + (long)p * dim + c * 8);
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      float f[8];
-      unpack8h(u[s], f);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] += f[q];
-    }
-    const float ww = w[t * k + j];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] += ww * bf2f(f2bf(v[q]));
-  }
+  float acc[8];
+  moe_combine_slab_picks<S>(ws, slab_stride, w, pos, t, k, dim, c, acc);
   store8(out + (long)t * dim + c * 8, acc);
 }
 
@@ -281,26 +284,8 @@ __global__ void __launch_bounds__(512) moe_combine_add_rmsnorm_kernel(
   __shared__ float red[16];
   const int t = blockIdx.x, c = threadIdx.x;
   const long off = (long)t * dim + c * 8;
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int j = 0; j < k; ++j) {
-    const int p = pos[t * k + j];
-    if (p < 0) continue;
-    uint4 u[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-      u[s] = *reinterpret_cast<const uint4*>(ws + s * slab_stride + (long)p * dim + c * 8);
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      float f[8];
-      unpack8h(u[s], f);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] += f[q];
-    }
-    const float ww = w[t * k + j];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) acc[q] += ww * bf2f(f2bf(v[q]));
-  }
+  float acc[8];
+  moe_combine_slab_picks<S>(ws, slab_stride, w, pos, t, k, dim, c, acc);
   float r[8], x[8], ss = 0.f;
   load8(residual + off, r);
 #pragma unroll

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Compare the generated device code of the bf16 GEMM families between two source trees.
+"""Compare the generated device code of kernel files between two source trees.
 
-Compiles gemm_tiles.hip, gemm8p.hip, gemm4w.hip and gemm4wp.hip of each tree with build.py's
-kernel flags plus ``--cuda-device-only -S`` (no GPU needed, about a minute per file), splits
-the assembly per kernel, strips comments / directives / metadata, maps kernel names whose
+Compiles the bf16 GEMM families (gemm_tiles.hip, gemm8p.hip, gemm4w.hip, gemm4wp.hip: the
+default) or the ``--files`` of csrc/kernels named, in each tree, with build.py's kernel flags
+plus ``--cuda-device-only -S`` (no GPU needed, about a minute per file). It splits the
+assembly per kernel, strips comments / directives / metadata, maps kernel names whose
 template parameters changed (``--map``), and reports per kernel ``identical`` or ``differs``
 with the resource figures of both sides (VGPRs, AGPRs, SGPRs, scratch, LDS, instruction
 count). It compares text and counts lines; it does not look at which instructions appear.
 
     python scripts/gemm_asm_compare.py BASE_TREE NEW_TREE [--md OUT.md] [--work DIR]
-        [--map 'REGEX=REPLACEMENT' ...]      # applied to BASE's demangled kernel names
-        [--files gemm8p.hip,...] [--diff N]  # a subset; N unified-diff lines per differing kernel
+        [--map 'REGEX=REPLACEMENT' ...]      # applied to BASE's demangled kernel names; the
+                                             # GEMM files' renames are built in
+        [--files rope_cache.hip,...]         # any .hip files of csrc/kernels instead
+        [--diff N]                           # N unified-diff lines per differing kernel
 
 Exit status 1 if a kernel is missing on either side or a resource figure differs.
 """
@@ -97,8 +100,19 @@ def parse(asm: Path) -> dict:
     for mangled, body in bodies.items():
         fields = {f: int(meta[mangled].get(f, "0")) for f in FIELDS}
         fields["instructions"] = sum(1 for s in body if not s.endswith(":"))
-        out[re.sub(r"^void ", "", dm[mangled]).split("(")[0]] = (body, fields)
+        out[kernel_name(dm[mangled])] = (body, fields)
     return out
+
+
+def kernel_name(demangled: str) -> str:
+    """``void f<2, (E)1>(int*)`` -> ``f<2, (E)1>``: cut at the argument list, which opens
+    outside the template brackets (an enum argument has parentheses of its own)."""
+    s, depth = re.sub(r"^void ", "", demangled), 0
+    for i, ch in enumerate(s):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            return s[:i]
+    return s
 
 
 def main():
@@ -107,14 +121,21 @@ def main():
     ap.add_argument("new", type=Path)
     ap.add_argument("--work", type=Path, default=Path("build") / "asm_compare")
     ap.add_argument("--md", type=Path, help="also write the table as markdown")
-    ap.add_argument("--map", action="append", default=list(DEFAULT_MAPS))
+    ap.add_argument("--map", action="append", default=[])
     ap.add_argument("-j", type=int, default=8)
-    ap.add_argument("--files", default=",".join(FILES), help="comma-separated subset")
+    ap.add_argument("--files", default=",".join(FILES),
+                    help="comma-separated .hip files of csrc/kernels")
     ap.add_argument("--diff", type=int, default=0, metavar="N",
                     help="print the first N unified-diff lines of each differing kernel")
     a = ap.parse_args()
-    maps = [m.split("=", 1) for m in a.map]
-    files = [f for f in FILES if f in a.files.split(",")]
+    files = [f for f in a.files.split(",") if f]
+    # the built-in renames belong to the GEMM families
+    builtin = DEFAULT_MAPS if set(files) & set(FILES) else ()
+    maps = [m.split("=", 1) for m in (*builtin, *a.map)]
+    for f in files:
+        for tree in (a.base, a.new):
+            if not f.endswith(".hip") or not (tree / "csrc" / "kernels" / f).is_file():
+                ap.error(f"--files: no {f} in {tree / 'csrc' / 'kernels'}")
     with cf.ThreadPoolExecutor(max_workers=a.j) as ex:
         futs = {(side, f): ex.submit(compile_asm, tree, f, a.work)
                 for side, tree in (("base", a.base), ("new", a.new)) for f in files}

@@ -56,6 +56,10 @@ def ulps(a, b):
 def test_rope_and_cache_extras(gpu, hq, hkv, hd, mode):
     """7 rows of a strided QKV buffer, one of them without a cache slot; head counts that
     fill whole waves, a fraction of one, and (9 heads of 8 lanes) straddle them."""
+    check_rope_and_cache_extras(gpu, hq, hkv, hd, mode, use_rope=True)
+
+
+def check_rope_and_cache_extras(gpu, hq, hkv, hd, mode, use_rope):
     torch.manual_seed(41)
     T, bs, nblk = 7, 16, 3
     n = (hq + 2 * hkv) * hd
@@ -68,10 +72,10 @@ def test_rope_and_cache_extras(gpu, hq, hkv, hd, mode):
     kc, vc = rnd(nblk, hkv, bs, hd, dev=gpu), rnd(nblk, hkv, bs, hd, dev=gpu)
     bias, qkn = extras(mode, hq, hkv, hd, gpu)
     ref, kc_r, vc_r = qkv.float().clone(), kc.float(), vc.float()
-    R.rope_and_cache(ref, pos, slots, cs, kc_r, vc_r, hq, hkv, hd,
+    R.rope_and_cache(ref, pos, slots, cs, kc_r, vc_r, hq, hkv, hd, use_rope,
                      bias=None if bias is None else bias.float(), qk_norm=f32(qkn))
     pad = buf[:, n:].clone()
-    q, k, v = ops.rope_and_cache(qkv, pos, slots, cs, kc, vc, hq, hkv, hd, bias=bias,
+    q, k, v = ops.rope_and_cache(qkv, pos, slots, cs, kc, vc, hq, hkv, hd, use_rope, bias=bias,
                                  qk_norm=qkn)
     torch.cuda.synchronize()
     close(qkv, ref)
@@ -85,16 +89,23 @@ def test_rope_and_cache_extras(gpu, hq, hkv, hd, mode):
     assert torch.equal(kc[m].float(), kc_r[m]) and torch.equal(vc[m].float(), vc_r[m])
 
 
+def test_rope_and_cache_extras_without_rope(gpu):
+    """``use_rope=False`` with a bias and QK-norm weights: the rows are biased and normalised
+    in place and k, v go to the cache unrotated."""
+    check_rope_and_cache_extras(gpu, 4, 2, 64, "both", use_rope=False)
+
+
 # ------------------------------------------------------------------------------ linear_rope_cache
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("splits,f16", [(1, False), (2, False), (2, True), (4, False),
-                                        (4, True), (8, False), (8, True)])
+@pytest.mark.parametrize("splits,f16", [(1, False), (2, False), (2, True), (3, False),
+                                        (4, False), (4, True), (8, False), (8, True)])
 def test_linear_rope_cache_extras(gpu, monkeypatch, splits, f16, mode):
-    """The slab consumer under forced plans: 2 / 4 / 8 slabs in fp32 and in fp16, and the
-    unsplit plan (bias in the GEMM epilogue, norm in ``rope_and_cache``)."""
+    """The slab consumer under forced plans: 2 / 4 / 8 slabs in fp32 and in fp16, 3 fp32 slabs
+    (the runtime-split loop, on a K that splits into 3 multiples of 64), and the unsplit plan
+    (bias in the GEMM epilogue, norm in ``rope_and_cache``)."""
     torch.manual_seed(42)
     hq, hkv, hd, bs, nblk = 32, 8, 128, 16, 4
-    M, K = 7, 1024
+    M, K = 7, 1536 if splits == 3 else 1024
     n = (hq + 2 * hkv) * hd
     assert 0 in G.SLAB16_TILES
     monkeypatch.setattr(G, "SLAB16", f16)
