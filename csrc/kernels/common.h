@@ -55,6 +55,44 @@ __device__ __forceinline__ void store8(u16* p, const float* f) {
   *reinterpret_cast<uint4*>(p) = v;
 }
 
+// FP8 KV cache (ops/reference.py quantize_kv): one OCP e4m3fn byte per element (gfx950's native
+// FP8, not the fnuz form), stored = rne(clamp(x * inv_scale, -448, 448)), read = byte * scale.
+// The clamp is written out: nothing here relies on the conversion to saturate. (A NaN comes
+// out of fminf / fmaxf as a bound, where the reference keeps it; K and V hold none.)
+typedef uint8_t fp8;
+constexpr float FP8_E4M3_MAX = 448.f;
+
+// 8 fp32 -> 8 e4m3fn bytes (one 8-byte store; v_cvt_pk_fp8_f32 rounds to nearest even)
+__device__ __forceinline__ void store8_fp8(fp8* p, const float* f, float inv_scale) {
+  float c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    c[j] = fminf(fmaxf(f[j] * inv_scale, -FP8_E4M3_MAX), FP8_E4M3_MAX);
+  uint2 v = make_uint2(0u, 0u);
+  v.x = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], v.x, false);
+  v.x = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], v.x, true);
+  v.y = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], v.y, false);
+  v.y = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], v.y, true);
+  *reinterpret_cast<uint2*>(p) = v;
+}
+
+// 2 e4m3fn bytes (the low or the high half of w) -> 2 bf16 in one word; exact, every e4m3fn
+// value is a bf16 value (v_cvt_scalef32_pk_bf16_fp8 with scale 1)
+template <bool HI>
+__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t w) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const bf16x2_t h = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI);
+  return __builtin_bit_cast(uint32_t, h);
+}
+
+// 16 e4m3fn bytes (one 16-B load) -> 16 bf16 in element order: lo = bytes 0..7, hi = 8..15
+__device__ __forceinline__ void fp8x16_to_bf16(const uint4 v, uint4& lo, uint4& hi) {
+  lo.x = fp8x2_to_bf16x2<false>(v.x); lo.y = fp8x2_to_bf16x2<true>(v.x);
+  lo.z = fp8x2_to_bf16x2<false>(v.y); lo.w = fp8x2_to_bf16x2<true>(v.y);
+  hi.x = fp8x2_to_bf16x2<false>(v.z); hi.y = fp8x2_to_bf16x2<true>(v.z);
+  hi.z = fp8x2_to_bf16x2<false>(v.w); hi.w = fp8x2_to_bf16x2<true>(v.w);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -265,6 +265,68 @@ extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, i
   DLI_RETURN_LAUNCH();
 }
 
+// The same slabs into an FP8 (e4m3fn) cache: see store8_fp8 of common.h
+template <int SPL, QkvSrc SRC, bool X>
+__global__ void __launch_bounds__(256) splitk_rope_cache_kv8_kernel(
+    u16* __restrict__ qkv, const float* __restrict__ ws, int splits, int T, int N,
+    const int* __restrict__ positions, const int* __restrict__ slot_mapping,
+    const float* __restrict__ cos_sin, fp8* __restrict__ k_cache, fp8* __restrict__ v_cache,
+    int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
+    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps,
+    float k_inv_scale, float v_inv_scale) {
+  qkv_rope_cache_body<SRC, SPL, X, fp8>(qkv, N, ws, splits, positions, slot_mapping, cos_sin,
+                                        k_cache, v_cache, T, hq, hkv, hd, block_size, use_rope,
+                                        bias, q_norm_w, k_norm_w, qk_eps, k_inv_scale,
+                                        v_inv_scale);
+}
+
+// dli_splitk_rope_cache_x with an FP8 cache; k_inv_scale / v_inv_scale as dli_rope_cache_kv8
+extern "C" int dli_splitk_rope_cache_kv8(void* qkv, const float* ws, int splits, int T, int N,
+                                         const int* positions, const int* slot_mapping,
+                                         const float* cos_sin, void* k_cache, void* v_cache,
+                                         int hq, int hkv, int hd, int block_size, int use_rope,
+                                         int fmt, const void* bias, const void* q_norm_w,
+                                         const void* k_norm_w, float qk_eps, float k_inv_scale,
+                                         float v_inv_scale, hipStream_t st) {
+  if (T <= 0) return 0;
+  if (hd % 16 || N != (hq + 2 * hkv) * hd || fmt < 0 || fmt > 1 || splits < 1 ||
+      (fmt == 1 && splits != 2 && splits != 4 && splits != 8) || !(k_inv_scale > 0.f) ||
+      !(v_inv_scale > 0.f))
+    return (int)hipErrorInvalidValue;
+  const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
+  const int blocks = (int)((total + 255) / 256);
+  const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
+  if (!qkv_extras_ok(bias, q_norm_w, k_norm_w, hd)) return (int)hipErrorInvalidValue;
+#define DLI_SRC8(S, F)                                                                      \
+  do {                                                                                      \
+    if (extras)                                                                             \
+      splitk_rope_cache_kv8_kernel<S, F, true><<<blocks, 256, 0, st>>>(                     \
+          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (fp8*)k_cache,     \
+          (fp8*)v_cache, hq, hkv, hd, block_size, use_rope, (const u16*)bias,               \
+          (const u16*)q_norm_w, (const u16*)k_norm_w, qk_eps, k_inv_scale, v_inv_scale);    \
+    else                                                                                    \
+      splitk_rope_cache_kv8_kernel<S, F, false><<<blocks, 256, 0, st>>>(                    \
+          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (fp8*)k_cache,     \
+          (fp8*)v_cache, hq, hkv, hd, block_size, use_rope, nullptr, nullptr, nullptr, 0.f, \
+          k_inv_scale, v_inv_scale);                                                        \
+  } while (0)
+  if (fmt == 1) {
+    switch (splits) {
+      case 2: DLI_SRC8(2, QkvSrc::SLAB16); break;
+      case 4: DLI_SRC8(4, QkvSrc::SLAB16); break;
+      default: DLI_SRC8(8, QkvSrc::SLAB16);
+    }
+  } else {
+    switch (splits) {
+      case 2: DLI_SRC8(2, QkvSrc::SLAB32); break;
+      case 4: DLI_SRC8(4, QkvSrc::SLAB32); break;
+      default: DLI_SRC8(0, QkvSrc::SLAB32);
+    }
+  }
+#undef DLI_SRC8
+  DLI_RETURN_LAUNCH();
+}
+
 extern "C" int dli_splitk_rope_cache(void* qkv, const float* ws, int splits, int T, int N,
                                      const int* positions, const int* slot_mapping,
                                      const float* cos_sin, void* k_cache, void* v_cache, int hq,

@@ -43,13 +43,16 @@ static inline bool qkv_extras_ok(const void* bias, const void* q_norm_w, const v
 // src unused) and splitk_rope_cache[_x]_kernel (slabs [S, T, row_stride] -> qkv rows).
 // SPL as in Slab8; the slab forms load positions[t] ahead of the slab loads, and the plain
 // ROWS form does not rewrite rows it did not change (v, and all of them with use_rope == 0).
-template <QkvSrc SRC, int SPL, bool X>
+// KV: the cache element, u16 (bf16, the rows as stored in qkv) or fp8 (common.h: the same
+// values times k_inv_scale / v_inv_scale, clamped, one 8-byte store per half).
+template <QkvSrc SRC, int SPL, bool X, typename KV = u16>
 __device__ __forceinline__ void qkv_rope_cache_body(
     u16* __restrict__ qkv, int row_stride, const void* src, int splits,
     const int* __restrict__ positions, const int* __restrict__ slot_mapping,
-    const float* __restrict__ cos_sin, u16* __restrict__ k_cache, u16* __restrict__ v_cache,
+    const float* __restrict__ cos_sin, KV* __restrict__ k_cache, KV* __restrict__ v_cache,
     int T, int hq, int hkv, int hd, int block_size, int use_rope, const u16* __restrict__ bias,
-    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps) {
+    const u16* __restrict__ q_norm_w, const u16* __restrict__ k_norm_w, float qk_eps,
+    [[maybe_unused]] float k_inv_scale = 1.f, [[maybe_unused]] float v_inv_scale = 1.f) {
   constexpr bool ROWS = SRC == QkvSrc::ROWS;
   const int lanes_per_head = hd >> 4;            // each lane: 8 dims + their partner 8 dims
   const int heads = hq + 2 * hkv;
@@ -130,8 +133,14 @@ __device__ __forceinline__ void qkv_rope_cache_body(
   if (is_q || k_cache == nullptr) return;
   const int slot = slot_mapping[t];
   if (slot < 0) return;
-  u16* dst = (is_k ? k_cache : v_cache) +
-             kv_cache_row(slot, block_size, hkv, is_k ? h - hq : h - hq - hkv, hd);
-  store8(dst + d0, x1);
-  store8(dst + half + d0, x2);
+  KV* dst = (is_k ? k_cache : v_cache) +
+            kv_cache_row(slot, block_size, hkv, is_k ? h - hq : h - hq - hkv, hd);
+  if constexpr (sizeof(KV) == 1) {
+    const float inv = is_k ? k_inv_scale : v_inv_scale;
+    store8_fp8(dst + d0, x1, inv);
+    store8_fp8(dst + half + d0, x2, inv);
+  } else {
+    store8(dst + d0, x1);
+    store8(dst + half + d0, x2);
+  }
 }

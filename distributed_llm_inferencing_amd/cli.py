@@ -6,6 +6,8 @@ launcher for an 8-GPU MI355X box.
 
     serve-master    [--port 8000]                       Flask master (dashboard + API)
     serve-worker    [--port 5000] [--gpu i]             one worker bound to one GPU (or CPU)
+                    (every serve-* command takes --kv-dtype bf16|fp8: the element type of
+                    the paged KV cache, default the environment's KV_CACHE_DTYPE or bf16)
     serve-node      --gpus N [--base-port 5000] [--master URL]
                     one worker process per GPU (--gpu i, port base+i; every GPU stays
                     visible to every worker so a ring formed over them by join-pipeline
@@ -43,7 +45,7 @@ import sys
 import time
 
 
-def node_commands(gpus: int, base_port: int = 5000, preload: str = ""):
+def node_commands(gpus: int, base_port: int = 5000, preload: str = "", kv_dtype=None):
     """[(argv, env)] of serve-node's workers: worker i selects GPU i of the operator's
     visibility mask with ``--gpu i`` (the mask, if any, is passed through unchanged, so
     ``HIP_VISIBLE_DEVICES=4,5,6,7 serve-node --gpus 4`` runs on physical GPUs 4-7) and sees
@@ -56,6 +58,8 @@ def node_commands(gpus: int, base_port: int = 5000, preload: str = ""):
         env.update(USE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
         cmd = [sys.executable, "-m", "distributed_llm_inferencing_amd.worker.server",
                "--port", str(base_port + i), "--gpu", str(i), "--preload", preload]
+        if kv_dtype:
+            cmd += ["--kv-dtype", kv_dtype]
         out.append((cmd, env))
     return out
 
@@ -69,9 +73,11 @@ def _serve_node(argv):
     ap.add_argument("--base-port", type=int, default=5000)
     ap.add_argument("--master", default=None, help="e.g. http://127.0.0.1:8000")
     ap.add_argument("--preload", default="")
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     a = ap.parse_args(argv)
     procs = []
-    for i, (cmd, env) in enumerate(node_commands(a.gpus, a.base_port, a.preload)):
+    for i, (cmd, env) in enumerate(node_commands(a.gpus, a.base_port, a.preload, a.kv_dtype)):
         procs.append(subprocess.Popen(cmd, env=env))
     if a.master:
         for i in range(a.gpus):
@@ -109,6 +115,8 @@ def _serve_pipeline(argv):
                          "<dir>/shard_<r>/model.safetensors (layers from its metadata.json)")
     ap.add_argument("--no-shard-report", action="store_true",
                     help="DP replica: serve the model as a plain node (no shard rows)")
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     a = ap.parse_args(argv)
     import torch
     from .config import get_settings
@@ -121,7 +129,7 @@ def _serve_pipeline(argv):
         torch.cuda.set_device(local)
     eng = DistributedPipelineEngine(a.model, dev, max_batch=a.max_batch,
                                     max_model_len=a.max_model_len, policy=a.policy,
-                                    shard_dir=a.shard_dir)
+                                    shard_dir=a.shard_dir, kv_dtype=a.kv_dtype)
     eng.warmup()
     if eng.rank != 0:
         eng.serve()
@@ -177,6 +185,8 @@ def _serve_expert(argv):
     ap.add_argument("--model-dir", default=None,
                     help="exported weights (shard-model output or a HF directory): each rank "
                          "reads all attention tensors and only its own experts' rows")
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     a = ap.parse_args(argv)
     from . import launch
     if not launch.under_launcher():
@@ -210,7 +220,8 @@ def _serve_expert_rank(a):
     dev = torch.device("cuda", local) if cuda else torch.device("cpu")
     kw = {} if cuda else {"num_blocks": 512, "dtype": torch.float32}
     eng = ExpertParallelEngine(a.model, dev, max_batch=a.max_batch,
-                               max_model_len=a.max_model_len, model_dir=a.model_dir, **kw)
+                               max_model_len=a.max_model_len, model_dir=a.model_dir,
+                               kv_dtype=a.kv_dtype, **kw)
     eng.warmup()
     logging.basicConfig(level=logging.INFO)
     s = get_settings()
@@ -247,6 +258,8 @@ def _serve_cluster(argv):
     ap.add_argument("--base-port", type=int, default=5000)
     ap.add_argument("--master", default=None)
     ap.add_argument("--max-batch", type=int, default=256)
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     a, extra = ap.parse_known_args(argv)
     procs = []
     plan = cluster_plan(a.gpus, a.dp, a.base_port)
@@ -257,7 +270,8 @@ def _serve_cluster(argv):
                f"--nproc-per-node={len(devs.split(','))}", "--master-addr", "127.0.0.1",
                "--master-port", str(rdzv), "-m", "distributed_llm_inferencing_amd.cli",
                "serve-pipeline", "--model", a.model, "--port", str(port),
-               "--max-batch", str(a.max_batch), "--no-shard-report", *extra]
+               "--max-batch", str(a.max_batch), "--no-shard-report",
+               *(["--kv-dtype", a.kv_dtype] if a.kv_dtype else []), *extra]
         procs.append(subprocess.Popen(cmd, env=env))
     if a.master:
         for j, _devs, port, _ in plan:

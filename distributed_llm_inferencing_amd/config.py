@@ -11,7 +11,8 @@ reference (worker, ``worker/app.py:19-30``):
 new:
     NUM_GPUS, PIPELINE_STAGES, DP_REPLICAS, DISPATCH_WORKERS, QUEUE_BACKEND (inproc|sqlite|redis),
     TRANSPORT (rccl|gloo|loopback), MAX_NEW_TOKENS, KV_CACHE_FRACTION,
-    MASTER_DB, MAX_BATCH, DLI_FAULT (fault-injection spec, see utils/faults.py)
+    MASTER_DB, MAX_BATCH, DLI_FAULT (fault-injection spec, see utils/faults.py),
+    KV_CACHE_DTYPE (bf16|fp8: the paged KV cache's element type)
 """
 from __future__ import annotations
 
@@ -62,6 +63,7 @@ class Settings:
     max_new_tokens: int = 0          # 0 -> use the reference's max_length=100 rule
     max_length: int = 100            # reference default, prompt included (views.py:351)
     kv_cache_fraction: float = 0.85
+    kv_cache_dtype: str = "bf16"     # bf16 | fp8 (engine/kv_cache.py)
     master_db: str = str(REPO_ROOT / "db.sqlite3")
     max_batch: int = 256
     # master dispatcher threads = requests in flight to workers (each blocks on one HTTP
@@ -90,6 +92,9 @@ class Settings:
         s.transport = os.environ.get("TRANSPORT", s.transport)
         s.max_new_tokens = _env_int("MAX_NEW_TOKENS", s.max_new_tokens)
         s.kv_cache_fraction = _env_float("KV_CACHE_FRACTION", s.kv_cache_fraction)
+        s.kv_cache_dtype = (os.environ.get("KV_CACHE_DTYPE", "") or s.kv_cache_dtype).strip().lower()
+        if s.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"KV_CACHE_DTYPE={s.kv_cache_dtype!r}: expected bf16 or fp8")
         s.master_db = os.environ.get("MASTER_DB", s.master_db)
         s.max_batch = _env_int("MAX_BATCH", s.max_batch)
         s.dispatch_workers = _env_int("DISPATCH_WORKERS", s.dispatch_workers)

@@ -20,7 +20,7 @@ from ..models.configs import ModelConfig, get_config
 from ..models.model import TransformerLM
 from ..runtime import BlockManager
 from ..tokenizer import load_tokenizer
-from .kv_cache import KVCache, auto_num_blocks
+from .kv_cache import KVCache, auto_num_blocks, kv_element_bytes, resolve_kv_dtype
 from .runner import StageRunner
 from .scheduler import Scheduler
 from .sequence import RequestOutput, SamplingParams, Sequence
@@ -102,7 +102,10 @@ class LLMEngine:
                  params: Optional[Dict[str, torch.Tensor]] = None, tokenizer_path=None,
                  max_prefill_tokens: int = 16384, num_layers: Optional[int] = None,
                  lm: Optional[TransformerLM] = None, lookahead: Optional[bool] = None,
-                 max_kv_tokens: Optional[int] = None, mixed_steps: Optional[bool] = None):
+                 max_kv_tokens: Optional[int] = None, mixed_steps: Optional[bool] = None,
+                 kv_dtype: Optional[str] = None, k_scale: float = 1.0, v_scale: float = 1.0):
+        # "bf16" | "fp8" (None: the environment variable KV_CACHE_DTYPE, default bf16)
+        self.kv_dtype = resolve_kv_dtype(kv_dtype)
         self.cfg = get_config(model, num_layers) if isinstance(model, str) else model
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -119,8 +122,10 @@ class LLMEngine:
         if num_blocks is None:
             # KV pool sized from free HBM, optionally capped
             num_blocks = auto_num_blocks(cfg, cfg.num_layers, block_size, self.device,
-                                         kv_fraction, cap_tokens=max_kv_tokens or 0)
-        self.kv = KVCache(cfg, cfg.num_layers, num_blocks, block_size, self.device, dtype)
+                                         kv_fraction, cap_tokens=max_kv_tokens or 0,
+                                         dtype_bytes=kv_element_bytes(self.kv_dtype))
+        self.kv = KVCache(cfg, cfg.num_layers, num_blocks, block_size, self.device, dtype,
+                          kv_dtype=self.kv_dtype, k_scale=k_scale, v_scale=v_scale)
         self.bm = BlockManager(num_blocks, block_size)
         # mixed prefill+decode steps (DLI_MIXED_STEPS=0 = off); engines in lockstep with peer
         # ranks (EP / TP) pass False so every rank's step kinds stay aligned
@@ -252,6 +257,7 @@ class LLMEngine:
     def memory_report(self) -> dict:
         rep = {"weights_bytes": self.model.param_bytes(), "kv_bytes": self.kv.nbytes,
                "kv_capacity_tokens": self.kv.capacity_tokens,
+               "kv_cache_dtype": self.kv.kv_dtype,
                "num_blocks": self.kv.num_blocks, "free_blocks": self.bm.num_free}
         if self.device.type == "cuda":
             free, total = torch.cuda.mem_get_info(self.device)

@@ -98,6 +98,7 @@ class TransformerLM:
             return self._llama_layers(x, b, kv_caches)
         residual = torch.empty_like(x)
         pending = None             # output of the previous sub-block awaiting its residual add
+        kvs = self._kv_scales(kv_caches)
         for li, lp in enumerate(self.layers):
             kc, vc = kv_caches[li] if kv_caches else (None, None)
             if cfg.arch == "gpt2":
@@ -110,7 +111,7 @@ class TransformerLM:
                      if pending is None else
                      ops.add_rmsnorm(pending, residual, lp["attn_norm"], cfg.norm_eps))
                 qkv = ops.linear(h, lp["wqkv"])
-            attn = self._attention(qkv, b, kc, vc)
+            attn = self._attention(qkv, b, kc, vc, kvs)
             if cfg.arch == "gpt2":
                 o = ops.linear(attn, lp["wo"], lp["bo"])
                 h = ops.add_layernorm(o, residual, lp["ln2_w"], lp["ln2_b"], cfg.norm_eps)
@@ -146,6 +147,7 @@ class TransformerLM:
         # split-K reduce + RMSNorm kernel runs between them (2 kernels fewer per layer)
         defer = (not b.is_prefill and self.tp_reduce is None and not cfg.is_moe
                  and ops.deferred_norm_ok(x))
+        kvs = self._kv_scales(kv_caches)
         for li, lp in enumerate(self.layers):
             kc, vc = kv_caches[li] if kv_caches else (None, None)
             if pending is not None:          # MoE output of the previous layer
@@ -166,8 +168,8 @@ class TransformerLM:
                 qkv = ops.linear_rope_cache(h, lp["wqkv"], b.positions, b.slot_mapping,
                                             self.cos_sin, kc, vc, cfg.num_heads,
                                             cfg.num_kv_heads, cfg.head_dim, bias=bqkv,
-                                            qk_norm=qkn)
-                attn = self._attend(qkv, b, kc, vc)
+                                            qk_norm=qkn, k_scale=kvs[0], v_scale=kvs[1])
+                attn = self._attend(qkv, b, kc, vc, kvs)
             if cfg.is_moe and self.tp_reduce is None and not defer:
                 # O projection + add + RMSNorm with the MoE gate of its output rows (one
                 # kernel when the slabs allow: ops.linear_add_rmsnorm route)
@@ -202,9 +204,17 @@ class TransformerLM:
             return None
         return ops.add_rmsnorm(y, residual, norm_w, eps)
 
-    def _attend(self, qkv, b: DeviceBatch, kc, vc) -> torch.Tensor:
+    @staticmethod
+    def _kv_scales(kv_caches) -> Tuple[float, float]:
+        """(k_scale, v_scale) of the stage's cache: ``KVCache.layers()`` carries them, a plain
+        list of (k, v) pairs has none (1, 1). Launch scalars, like the window."""
+        return (float(getattr(kv_caches, "k_scale", 1.0)),
+                float(getattr(kv_caches, "v_scale", 1.0)))
+
+    def _attend(self, qkv, b: DeviceBatch, kc, vc, kvs=(1.0, 1.0)) -> torch.Tensor:
         cfg = self.cfg
         win = cfg.sliding_window                 # 0 = full attention
+        ks, vs = kvs
         if b.is_prefill:
             if b.num_decode:                     # mixed step: decode rows, then prefill chunks
                 nd = b.num_decode
@@ -213,30 +223,32 @@ class TransformerLM:
                 ops.decode_attention(qkv[:nd], kc, vc, b.block_tables[:nd],
                                      b.context_lens[:nd], b.max_context_decode, cfg.num_heads,
                                      cfg.num_kv_heads, cfg.head_dim, self.scale, out=out[:nd],
-                                     window=win)
+                                     window=win, k_scale=ks, v_scale=vs)
                 ops.prefill_attention_paged(qkv[nd:], b.cu_seqlens_prefill,
                                             b.max_seqlen_prefill, b.context_lens[nd:],
                                             b.block_tables[nd:], kc, vc, cfg.num_heads,
                                             cfg.num_kv_heads, cfg.head_dim, self.scale,
-                                            out=out[nd:], window=win)
+                                            out=out[nd:], window=win, k_scale=ks, v_scale=vs)
                 return out
             if b.block_tables is not None:       # chunked prefill over the paged cache
                 return ops.prefill_attention_paged(qkv, b.cu_seqlens, b.max_seqlen,
                                                    b.context_lens, b.block_tables, kc, vc,
                                                    cfg.num_heads, cfg.num_kv_heads,
-                                                   cfg.head_dim, self.scale, window=win)
+                                                   cfg.head_dim, self.scale, window=win,
+                                                   k_scale=ks, v_scale=vs)
             return ops.prefill_attention(qkv, b.cu_seqlens, b.max_seqlen, cfg.num_heads,
                                          cfg.num_kv_heads, cfg.head_dim, self.scale,
                                          window=win)
         return ops.decode_attention(qkv, kc, vc, b.block_tables, b.context_lens, b.max_context,
                                     cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, self.scale,
-                                    window=win)
+                                    window=win, k_scale=ks, v_scale=vs)
 
-    def _attention(self, qkv, b: DeviceBatch, kc, vc) -> torch.Tensor:
+    def _attention(self, qkv, b: DeviceBatch, kc, vc, kvs=(1.0, 1.0)) -> torch.Tensor:
         cfg = self.cfg
         ops.rope_and_cache(qkv, b.positions, b.slot_mapping, self.cos_sin, kc, vc, cfg.num_heads,
-                           cfg.num_kv_heads, cfg.head_dim, use_rope=cfg.arch != "gpt2")
-        return self._attend(qkv, b, kc, vc)
+                           cfg.num_kv_heads, cfg.head_dim, use_rope=cfg.arch != "gpt2",
+                           k_scale=kvs[0], v_scale=kvs[1])
+        return self._attend(qkv, b, kc, vc, kvs)
 
     def _moe_local(self, h: torch.Tensor, lp: dict, layer: int, routing=None):
         """The layer's experts on this device. With ``routing`` (the gate computed in the O

@@ -361,13 +361,41 @@ def _qkv_extras(bias, qk_norm, n: int, hd: int):
     return bias, q_w, k_w, float(eps)
 
 
+_CPU_KV_DTYPES = (torch.bfloat16, torch.float16, torch.float32, R.FP8_KV)
+
+
+def kv_cache_is_fp8(k_cache, v_cache, k_scale: float = 1.0, v_scale: float = 1.0,
+                    native: bool = True) -> bool:
+    """Checks a paged cache pair and its scales before any kernel sees them; True for an FP8
+    (``float8_e4m3fn``) cache. The HIP kernels read bf16 or e4m3fn and nothing else (a
+    one-byte buffer handed to the bf16 kernels would be read as 2-byte elements, past its
+    end); the reference ops also take fp16 / fp32 caches. K and V share one dtype, scales
+    are > 0, and only an FP8 cache has scales other than 1."""
+    if not (k_scale > 0 and v_scale > 0):       # (NaN fails too)
+        raise ValueError(f"kv cache scales must be > 0, got {k_scale}, {v_scale}")
+    if k_cache is None or v_cache is None:
+        return False
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache is {k_cache.dtype} but v_cache is {v_cache.dtype}")
+    dt = k_cache.dtype
+    if dt not in ((torch.bfloat16, R.FP8_KV) if native else _CPU_KV_DTYPES):
+        raise ValueError(f"unsupported kv cache dtype {dt} (bfloat16 or float8_e4m3fn)")
+    fp8 = dt == R.FP8_KV
+    if not fp8 and (k_scale != 1.0 or v_scale != 1.0):
+        raise ValueError("k_scale / v_scale other than 1 need a float8_e4m3fn kv cache")
+    return fp8
+
+
 def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
                       use_rope: bool = True, plan: Optional[G.GemmPlan] = None, bias=None,
-                      qk_norm=None):
-    """qkv = x @ w.T with RoPE applied in place to q,k and k,v written to the paged cache.
+                      qk_norm=None, k_scale: float = 1.0, v_scale: float = 1.0):
+    """qkv = x @ w.T with RoPE applied in place to q,k and k,v written to the paged cache
+    (``k_scale`` / ``v_scale``: the scales of an FP8 cache, see ``rope_and_cache``).
     ``plan`` forces the GEMM plan (the autotuner times QKV candidates with this consumer).
     ``bias`` / ``qk_norm``: see ``rope_and_cache``; with split-K slabs the bias is added to
     their fp32 sum, before the one rounding that stands for the GEMM output."""
+    xr = x.residual if isinstance(x, NormedRows) else x
+    fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(xr))
     if isinstance(x, NormedRows):
         x = x.materialize()
     if plan is None:
@@ -380,7 +408,7 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
         else:
             qkv = _gemm_native(x, w, "none" if bias is None else "bias", bias=bias, plan=plan)
         rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
-                       use_rope, qk_norm=qk_norm)
+                       use_rope, qk_norm=qk_norm, k_scale=k_scale, v_scale=v_scale)
         return qkv
     M, K = x.shape
     Nn = w.shape[0]
@@ -388,6 +416,13 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
     fmt = _slab_gemm(x, w, p, ws)
     qkv = torch.empty(M, Nn, dtype=x.dtype, device=x.device)
     bs = k_cache.shape[2] if k_cache is not None else 16
+    if fp8:
+        bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
+        _native_call("dli_splitk_rope_cache_kv8", _p(qkv), _p(ws), p.splits, M, Nn,
+                     _p(positions), _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq,
+                     hkv, hd, bs, int(use_rope), fmt, _p(bias), _p(q_w), _p(k_w), eps,
+                     R.inv_scale(k_scale), R.inv_scale(v_scale), _st())
+        return qkv
     if bias is None and qk_norm is None:
         _native_call("dli_splitk_rope_cache", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
                      _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq, hkv, hd, bs,
@@ -412,9 +447,11 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     pipelined long-context kernel, head dim != 128. ``window`` > 0: sliding-window attention;
     the choice between the kernels follows the span a sequence can attend over,
     min(max_context, window). ``bias`` / ``qk_norm`` (Qwen2 / Qwen3, see ``rope_and_cache``)
-    are applied by the same kernel's prologue."""
+    are applied by the same kernel's prologue. An FP8 cache has no fused kernel: None."""
     xr = x.residual if isinstance(x, NormedRows) else x
     if hd != 128 or k_cache is None or not _use_native(xr):
+        return None
+    if kv_cache_is_fp8(k_cache, v_cache):
         return None
     p = _splitk_plan(xr, w)
     if p is not None and p.splits not in (2, 4):
@@ -505,17 +542,29 @@ def bias_act_(x, bias, act: str = "none"):
 
 # ----------------------------------------------------------------------------- RoPE / KV cache
 def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
-                   use_rope: bool = True, bias=None, qk_norm=None):
+                   use_rope: bool = True, bias=None, qk_norm=None, k_scale: float = 1.0,
+                   v_scale: float = 1.0):
     """In-place RoPE on q,k inside qkv + paged cache write. Returns views (q, k, v).
     ``bias`` [(hq+2hkv)*hd]: added to the rows first (Qwen2's QKV bias; rows that come from
     ``linear(x, w, bias)`` already hold it). ``qk_norm`` = (q_w [hd], k_w [hd], eps): every q
     and k head is RMS-normalised over its hd dims before the rotation (Qwen3); v is not.
-    Each step rounds to bf16: bias, norm, rotation."""
+    Each step rounds to bf16: bias, norm, rotation. A ``float8_e4m3fn`` cache receives
+    ``reference.quantize_kv`` of the k / v values stored in the rows, under the per-cache
+    scales ``k_scale`` / ``v_scale`` (stored = fp8(clamp(x / scale, +-448)))."""
+    fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(qkv))
     if not _use_native(qkv):
         return R.rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv,
-                                hd, use_rope, bias=bias, qk_norm=qk_norm)
+                                hd, use_rope, bias=bias, qk_norm=qk_norm, k_scale=k_scale,
+                                v_scale=v_scale)
     T = qkv.shape[0]
     bs = k_cache.shape[2] if k_cache is not None else 16
+    if fp8:
+        bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, (hq + 2 * hkv) * hd, hd)
+        _native_call("dli_rope_cache_kv8", _p(qkv), qkv.stride(0), _p(positions),
+                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs,
+                     int(use_rope), _p(bias), _p(q_w), _p(k_w), eps, R.inv_scale(k_scale),
+                     R.inv_scale(v_scale), _st())
+        return R.split_qkv(qkv, hq, hkv, hd)
     if bias is None and qk_norm is None:
         _native_call("dli_rope_cache", _p(qkv), qkv.stride(0), _p(positions),
                      _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs,
@@ -579,17 +628,21 @@ def prefill_set_pack(on: bool) -> bool:
 
 
 def prefill_attention_paged(qkv, cu_seqlens, max_seqlen: int, context_lens, block_tables,
-                            k_cache, v_cache, hq, hkv, hd, scale, out=None, window: int = 0):
+                            k_cache, v_cache, hq, hkv, hd, scale, out=None, window: int = 0,
+                            k_scale: float = 1.0, v_scale: float = 1.0):
     """Chunked prefill attention: each sequence's chunk of queries (packed rows of ``qkv``)
     attends over all ``context_lens[i]`` keys of the sequence in the paged cache — earlier
     chunks plus this one (already written by ``rope_and_cache``); [T, Hq*hd]. ``window`` > 0:
-    each query sees the last ``window`` keys up to its own position."""
+    each query sees the last ``window`` keys up to its own position. ``k_scale`` /
+    ``v_scale``: the scales of an FP8 cache (every chunk length then takes the 64-row kernel)."""
     window = max(int(window), 0)
     T = qkv.shape[0]
+    fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(qkv))
     if not _use_native(qkv):
         q = qkv[:, : hq * hd].reshape(T, hq, hd)
         o = R.prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens,
-                                      block_tables, scale, window).reshape(T, hq * hd)
+                                      block_tables, scale, window, k_scale,
+                                      v_scale).reshape(T, hq * hd)
         if out is not None:
             out.copy_(o)
             return out
@@ -597,6 +650,12 @@ def prefill_attention_paged(qkv, cu_seqlens, max_seqlen: int, context_lens, bloc
     if out is None:
         out = torch.empty(T, hq * hd, dtype=qkv.dtype, device=qkv.device)
     nseq = cu_seqlens.shape[0] - 1
+    if fp8:
+        _native_call("dli_prefill_attention_paged_kv8", _p(out), out.stride(0), _p(qkv),
+                     qkv.stride(0), _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache),
+                     _p(block_tables), block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd,
+                     k_cache.shape[2], scale, window, float(k_scale), float(v_scale), _st())
+        return out
     _native_call("dli_prefill_attention_paged_win", _p(out), out.stride(0), _p(qkv),
                  qkv.stride(0), _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache),
                  _p(block_tables), block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd,
@@ -627,16 +686,18 @@ def decode_num_splits(B: int, hkv: int, max_context: int) -> int:
 
 def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_context: int,
                      hq, hkv, hd, scale, out=None, num_splits: Optional[int] = None,
-                     window: int = 0):
+                     window: int = 0, k_scale: float = 1.0, v_scale: float = 1.0):
     """One query per row of ``qkv`` (rows = sequences) against its paged KV; [B, Hq*hd].
     ``window`` > 0: sliding-window attention, sequence b attends over the keys
-    [max(0, context_lens[b] - window), context_lens[b])."""
+    [max(0, context_lens[b] - window), context_lens[b]). ``k_scale`` / ``v_scale``: the
+    scales of an FP8 cache (the wave-per-item kernel of attention_decode_fp8.hip)."""
     B = qkv.shape[0]
     window = max(int(window), 0)
+    fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(qkv))
     if not _use_native(qkv):
         q = qkv[:, : hq * hd].reshape(B, hq, hd)
         o = R.decode_attention(q, k_cache, v_cache, block_tables, context_lens,
-                               scale, window).reshape(B, hq * hd)
+                               scale, window, k_scale, v_scale).reshape(B, hq * hd)
         if out is not None:
             out.copy_(o)
             return out
@@ -650,6 +711,12 @@ def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_cont
         nbytes = B * hq * num_splits * (hd + 2) * 4
         ws = G.workspace(qkv.device, nbytes)
     bs = k_cache.shape[2]
+    if fp8:
+        _native_call("dli_decode_attention_kv8", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
+                     _p(v_cache), _p(block_tables), block_tables.stride(0), _p(context_lens), B,
+                     hq, hkv, hd, bs, scale, max_context, num_splits, _p(ws), window,
+                     float(k_scale), float(v_scale), _st())
+        return out
     _native_call("dli_decode_attention_win", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
                  _p(v_cache), _p(block_tables), block_tables.stride(0), _p(context_lens), B, hq,
                  hkv, hd, bs, scale, max_context, num_splits, _p(ws), window, _st())

@@ -72,6 +72,14 @@ _SIGS = {
     "dli_splitk_rope_cache_x": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, P],
     "dli_decode_attention_fused_x": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
                                      P, P, P, F, P],
+    # FP8 (e4m3fn) KV cache: the two writers (..., extras, 1/k_scale, 1/v_scale, stream) and
+    # the two readers (..., window, k_scale, v_scale, stream)
+    "dli_rope_cache_kv8": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, F, F, P],
+    "dli_splitk_rope_cache_kv8": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, F,
+                                  F, P],
+    "dli_decode_attention_kv8": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, F, F, P],
+    "dli_prefill_attention_paged_kv8": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I, F,
+                                        F, P],
     "dli_moe_route": [P, P, P, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

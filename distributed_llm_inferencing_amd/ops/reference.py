@@ -163,20 +163,52 @@ def split_qkv(qkv: torch.Tensor, hq: int, hkv: int, hd: int):
     return q, k, v
 
 
+# FP8 KV cache: one OCP e4m3fn byte per element and one fp32 scale per cache (K, V).
+#   stored = fp8_rne(clamp(x * (1 / scale), -448, 448)),   read = float(byte) * scale
+# x is the bf16 value of the qkv row (K after the rotation), 1 / scale is computed once in
+# fp32. The clamp is part of the definition: torch's cast gives NaN above the e4m3 range.
+FP8_KV = torch.float8_e4m3fn
+FP8_KV_MAX = 448.0
+
+
+def inv_scale(scale: float) -> float:
+    """1 / scale as the fp32 value every writer (the HIP kernels too) multiplies by."""
+    return float(torch.tensor(1.0, dtype=torch.float32)
+                 / torch.tensor(float(scale), dtype=torch.float32))
+
+
+def quantize_kv(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The FP8 cache elements of ``x`` under ``scale`` (``float8_e4m3fn``, same shape)."""
+    y = (x.float() * inv_scale(scale)).clamp(-FP8_KV_MAX, FP8_KV_MAX)
+    return y.to(FP8_KV)
+
+
+def dequantize_kv(c: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """fp32 values of cache elements: FP8 bytes times ``scale``; other dtypes as they are."""
+    return c.float() * float(scale) if c.dtype == FP8_KV else c.float()
+
+
 def write_kv(k: torch.Tensor, v: torch.Tensor, slot_mapping: torch.Tensor,
-             k_cache: torch.Tensor, v_cache: torch.Tensor) -> None:
+             k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: float = 1.0,
+             v_scale: float = 1.0) -> None:
     bs = k_cache.shape[2]
     slots = slot_mapping.long()
     valid = slots >= 0
     slots, kk, vv = slots[valid], k[valid], v[valid]
     blk, off = slots // bs, slots % bs
+    if k_cache.dtype == FP8_KV:
+        k_cache[blk, :, off, :] = quantize_kv(kk, k_scale)
+        v_cache[blk, :, off, :] = quantize_kv(vv, v_scale)
+        return
     k_cache[blk, :, off, :] = kk.to(k_cache.dtype)
     v_cache[blk, :, off, :] = vv.to(v_cache.dtype)
 
 
 def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache,
-                   hq: int, hkv: int, hd: int, use_rope: bool = True, bias=None, qk_norm=None):
-    """Rotates q and k IN PLACE inside ``qkv`` and writes k/v to the paged cache.
+                   hq: int, hkv: int, hd: int, use_rope: bool = True, bias=None, qk_norm=None,
+                   k_scale: float = 1.0, v_scale: float = 1.0):
+    """Rotates q and k IN PLACE inside ``qkv`` and writes k/v to the paged cache (an FP8
+    cache receives ``quantize_kv`` of the rows under ``k_scale`` / ``v_scale``).
     Returns strided views (q [T,Hq,hd], k [T,Hkv,hd], v [T,Hkv,hd]) into ``qkv``.
     ``bias`` [(Hq+2Hkv)*hd] (Qwen2) is added to the rows first; ``qk_norm`` = (q_w [hd],
     k_w [hd], eps) (Qwen3) then normalises every q and k head (``rmsnorm`` over its hd dims)
@@ -192,7 +224,7 @@ def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache,
         q.copy_(apply_rope(q, positions, cos_sin))
         k.copy_(apply_rope(k, positions, cos_sin))
     if k_cache is not None:
-        write_kv(k, v, slot_mapping, k_cache, v_cache)
+        write_kv(k, v, slot_mapping, k_cache, v_cache, k_scale, v_scale)
     return q, k, v
 
 
@@ -224,18 +256,23 @@ def prefill_attention(q, k, v, cu_seqlens: torch.Tensor, scale: float,
     return out
 
 
-def gather_kv(k_cache, v_cache, block_table: torch.Tensor, ctx_len: int):
-    """Contiguous [ctx, Hkv, hd] K and V for one sequence from the paged cache."""
+def gather_kv(k_cache, v_cache, block_table: torch.Tensor, ctx_len: int,
+              k_scale: float = 1.0, v_scale: float = 1.0):
+    """Contiguous [ctx, Hkv, hd] K and V for one sequence from the paged cache (an FP8
+    cache comes back dequantised: fp32, bytes times the scale)."""
     bs = k_cache.shape[2]
     nblk = (ctx_len + bs - 1) // bs
     blocks = block_table[:nblk].long()
     kk = k_cache[blocks].permute(0, 2, 1, 3).reshape(nblk * bs, k_cache.shape[1], -1)[:ctx_len]
     vv = v_cache[blocks].permute(0, 2, 1, 3).reshape(nblk * bs, v_cache.shape[1], -1)[:ctx_len]
+    if k_cache.dtype == FP8_KV:
+        return dequantize_kv(kk, k_scale), dequantize_kv(vv, v_scale)
     return kk, vv
 
 
 def prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens, block_tables,
-                            scale: float, window: int = 0) -> torch.Tensor:
+                            scale: float, window: int = 0, k_scale: float = 1.0,
+                            v_scale: float = 1.0) -> torch.Tensor:
     """Chunked prefill: the queries q[cu[i]:cu[i+1]] sit at positions [ctx-L, ctx) of
     sequence i and attend causally over its ctx = context_lens[i] cached keys (``window``
     > 0: over the last ``window`` of them up to their own position, as ``prefill_attention``)."""
@@ -248,7 +285,7 @@ def prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens, block
         if e <= s:
             continue
         L, ctx = e - s, lens[i]
-        kk, vv = gather_kv(k_cache, v_cache, block_tables[i], ctx)
+        kk, vv = gather_kv(k_cache, v_cache, block_tables[i], ctx, k_scale, v_scale)
         kk = kk.float().transpose(0, 1).repeat_interleave(rep, 0)   # [Hq, ctx, hd]
         vv = vv.float().transpose(0, 1).repeat_interleave(rep, 0)
         qs = q[s:e].float().transpose(0, 1)                          # [Hq, L, hd]
@@ -264,7 +301,7 @@ def prefill_attention_paged(q, k_cache, v_cache, cu_seqlens, context_lens, block
 
 
 def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale,
-                     window: int = 0) -> torch.Tensor:
+                     window: int = 0, k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     """q [B,Hq,hd] single query per sequence against its paged cache. ``window`` > 0: the
     query sits at position L - 1 and sees the keys [max(0, L - window), L)."""
     out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
@@ -275,7 +312,7 @@ def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale,
         if L <= 0:
             out[b] = 0
             continue
-        kk, vv = gather_kv(k_cache, v_cache, block_tables[b], L)
+        kk, vv = gather_kv(k_cache, v_cache, block_tables[b], L, k_scale, v_scale)
         kk = kk.float().transpose(0, 1).repeat_interleave(rep, 0)   # [Hq, L, hd]
         vv = vv.float().transpose(0, 1).repeat_interleave(rep, 0)
         sc = (kk @ q[b].float().unsqueeze(-1)).squeeze(-1) * scale  # [Hq, L]

@@ -265,7 +265,8 @@ class ExpertParallelEngine:
     def __init__(self, model: str, device, max_batch: int = 256, max_model_len: int = 2048,
                  seed: int = 0, num_blocks: Optional[int] = None, dtype=torch.bfloat16,
                  max_prefill_tokens: int = 16384, lookahead: Optional[bool] = None,
-                 comm: Optional[str] = None, model_dir: Optional[str] = None):
+                 comm: Optional[str] = None, model_dir: Optional[str] = None,
+                 kv_dtype: Optional[str] = None):
         from .transport import init_distributed
         dev = torch.device(device)
         self.rank, self.world = init_distributed(device=dev if dev.type == "cuda" else None)
@@ -319,7 +320,7 @@ class ExpertParallelEngine:
                                 max_model_len=max_model_len, num_blocks=num_blocks,
                                 use_graphs=graphs, lm=lm,
                                 max_prefill_tokens=max_prefill_tokens, lookahead=lookahead,
-                                mixed_steps=False)
+                                mixed_steps=False, kv_dtype=kv_dtype)
         self.max_batch = max_batch
         self.device = dev
         self.steps = 0

@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 
 from ..engine.batch import DECODE, EMPTY, HEADER_LEN, PREFILL, STOP, StepMeta
-from ..engine.kv_cache import KVCache, auto_num_blocks
+from ..engine.kv_cache import KVCache, auto_num_blocks, kv_element_bytes, resolve_kv_dtype
 from ..engine.llm_engine import EngineStats, seq_to_output
 from ..engine.runner import StageRunner
 from ..engine.scheduler import Scheduler
@@ -108,7 +108,8 @@ class StageWorker:
     def __init__(self, cfg: ModelConfig, plan: StagePlan, device, num_blocks: int,
                  block_size: int, max_batch: int, table_width: int, seed: int = 0,
                  use_graphs: Optional[bool] = None, params=None, dtype=torch.bfloat16,
-                 vocab_slice: Optional[Tuple[int, int]] = None, max_tokens: int = 0):
+                 vocab_slice: Optional[Tuple[int, int]] = None, max_tokens: int = 0,
+                 kv_dtype: Optional[str] = None):
         self.cfg, self.plan = cfg, plan
         self.device = torch.device(device)
         self.max_batch = max_batch
@@ -131,8 +132,9 @@ class StageWorker:
                 del full
             self.model.vocab_parallel = True
             self.model.vocab_offset = lo
+        # "bf16" | "fp8" (None: the environment variable KV_CACHE_DTYPE, default bf16)
         self.kv = KVCache(cfg, plan.end_layer - plan.start_layer, num_blocks, block_size,
-                          self.device, dtype)
+                          self.device, dtype, kv_dtype=resolve_kv_dtype(kv_dtype))
         self.runner = StageRunner(self.model, self.kv, max_batch, table_width, use_graphs)
         self.tick_counts: Dict[int, int] = {}     # non-head ranks: steps run, by kind
         self._samp = None                         # pinned staging ring of _sampling
@@ -224,7 +226,7 @@ H_VP = 13          # ctrl header word: 1 = vocab-parallel head for this step
 
 def _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction, cap_tokens,
                            vocab_slice: Optional[Tuple[int, int]] = None,
-                           loaded: bool = False):
+                           loaded: bool = False, kv_dtype: Optional[str] = None):
     """KV blocks of this stage's pool, sized before its weights are loaded: the stage's own
     parameter bytes (plus its vocab-parallel head slice) are still to come, and with every
     rank on one device (``DLI_SAME_DEVICE=1``) so are every other rank's — summed over the
@@ -242,7 +244,8 @@ def _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction, cap_token
         dist.all_reduce(t, group=_cpu_group())
         pending = int(t.item())
     return auto_num_blocks(cfg, plan.end_layer - plan.start_layer, block_size, device,
-                           kv_fraction, cap_tokens=cap_tokens, pending_bytes=pending)
+                           kv_fraction, cap_tokens=cap_tokens, pending_bytes=pending,
+                           dtype_bytes=kv_element_bytes(kv_dtype))
 
 
 _CPU_GROUP = None
@@ -755,7 +758,7 @@ def build_stage(cfg: ModelConfig, rank: int, world: int, device, max_batch: int,
                 num_blocks: Optional[int] = None, dtype=torch.bfloat16,
                 vocab_parallel: bool = False, microbatches: Optional[int] = None,
                 max_tokens: int = 0, shard_dir: Optional[str] = None,
-                max_kv_tokens: int = 0):
+                max_kv_tokens: int = 0, kv_dtype: Optional[str] = None):
     if shard_dir is not None:
         from ..shard.writer import stage_plan_from_metadata
         plans = [stage_plan_from_metadata(read_shard_dir(shard_dir, i, world)[1])
@@ -773,14 +776,14 @@ def build_stage(cfg: ModelConfig, rank: int, world: int, device, max_batch: int,
         # the same block ids (the head's allocator), so all take the smallest pool
         cap = _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction,
                                      cap_tokens=max_kv_tokens, vocab_slice=vs,
-                                     loaded=params is not None)
+                                     loaded=params is not None, kv_dtype=kv_dtype)
         t = torch.tensor([cap], dtype=torch.int64,
                          device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)     # block ids are global: same pool size
         num_blocks = int(t.item())
     stage = StageWorker(cfg, plan, device, num_blocks, block_size, max_batch, table_width,
                         seed=seed, use_graphs=use_graphs, dtype=dtype, vocab_slice=vs,
-                        max_tokens=max_tokens, params=params)
+                        max_tokens=max_tokens, params=params, kv_dtype=kv_dtype)
     return stage, plans, num_blocks, table_width
 
 
@@ -793,7 +796,9 @@ class DistributedPipelineEngine:
                  block_size: int = 16, policy: str = "balanced", seed: int = 0,
                  use_graphs=None, max_prefill_tokens: int = 16384, num_blocks=None,
                  dtype=torch.bfloat16, vocab_parallel: Optional[bool] = None,
-                 shard_dir: Optional[str] = None, max_kv_tokens: int = 0):
+                 shard_dir: Optional[str] = None, max_kv_tokens: int = 0,
+                 kv_dtype: Optional[str] = None):
+        self.kv_dtype = resolve_kv_dtype(kv_dtype)
         self.rank, self.world = init_distributed(device=torch.device(device)
                                                  if torch.device(device).type == "cuda" else None)
         if shard_dir is not None:
@@ -816,7 +821,8 @@ class DistributedPipelineEngine:
             self.cfg, self.rank, self.world, self.device, max_batch, max_model_len, block_size,
             policy=policy, seed=seed, use_graphs=use_graphs, num_blocks=num_blocks, dtype=dtype,
             vocab_parallel=self.vocab_parallel, microbatches=self.microbatches,
-            max_tokens=max_tokens, shard_dir=shard_dir, max_kv_tokens=max_kv_tokens)
+            max_tokens=max_tokens, shard_dir=shard_dir, max_kv_tokens=max_kv_tokens,
+            kv_dtype=self.kv_dtype)
         esz = torch.empty(0, dtype=dtype).element_size()
         D = self.cfg.hidden_size
         # mailbox sizes of the IPC data plane: a whole step's hidden rows on r -> r + 1; the
@@ -886,8 +892,10 @@ class LocalPipeline:
                  max_model_len: int = 512, block_size: int = 16, num_blocks: int = 256,
                  policy: str = "even", seed: int = 0, use_graphs=None, params=None,
                  dtype=torch.bfloat16, plans: Optional[List[StagePlan]] = None,
-                 stage_params: Optional[List[Dict[str, torch.Tensor]]] = None, tokenizer=None):
+                 stage_params: Optional[List[Dict[str, torch.Tensor]]] = None, tokenizer=None,
+                 kv_dtype: Optional[str] = None):
         self.cfg = get_config(model) if isinstance(model, str) else model
+        self.kv_dtype = resolve_kv_dtype(kv_dtype)
         self.N = num_stages
         self.plans = plans or plan_stages(self.cfg, num_stages, policy)
         tw = -(-max_model_len // block_size)
@@ -900,7 +908,7 @@ class LocalPipeline:
                 sp = {k: v for k, v in params.items() if _param_in_stage(k, p, self.cfg)}
             self.stages.append(StageWorker(self.cfg, p, device, num_blocks, block_size,
                                            max_batch, tw, seed, use_graphs, params=sp,
-                                           dtype=dtype))
+                                           dtype=dtype, kv_dtype=self.kv_dtype))
         self.sched = Scheduler(BlockManager(num_blocks, block_size), max_seqs_per_mb=max_batch,
                                num_microbatches=num_stages, eos_token_id=self.cfg.eos_token_id,
                                max_model_len=max_model_len, table_width=tw,

@@ -78,6 +78,11 @@ class WorkerState:
                                   max_model_len=2048 if gpu else 512,
                                   num_blocks=None if gpu else 512)
         self.engine_kwargs.update(engine_kwargs or {})
+        # the KV cache's element type of every engine this worker builds (bf16 | fp8); an
+        # unknown value stops the worker here, not at the first /load_model
+        from ..engine.kv_cache import resolve_kv_dtype
+        self.engine_kwargs["kv_dtype"] = resolve_kv_dtype(
+            self.engine_kwargs.get("kv_dtype") or getattr(settings, "kv_cache_dtype", None))
         if gpu and self.engine_kwargs.get("num_blocks") is None:
             # a worker may serve several models (/load_model per name): each engine's KV
             # pool is capped at max_batch x max_model_len tokens (DLI_KV_MAX_TOKENS
@@ -225,7 +230,8 @@ class WorkerState:
                                             max_model_len=kw["max_model_len"],
                                             num_blocks=kw["num_blocks"], shard_dir=shard_dir,
                                             dtype=_shard_dtype(shard_dir, rank),
-                                            max_kv_tokens=kw.get("max_kv_tokens") or 0)
+                                            max_kv_tokens=kw.get("max_kv_tokens") or 0,
+                                            kv_dtype=kw.get("kv_dtype"))
             eng.warmup()
             self._pipe_engine = eng
             ch = eng.channel
@@ -397,7 +403,8 @@ class WorkerState:
             pipe = LocalPipeline(cfg, len(plans), device=self.device, max_batch=kw["max_batch"],
                                  max_model_len=kw["max_model_len"],
                                  num_blocks=kw["num_blocks"] or 4096, params=params,
-                                 plans=plans, tokenizer=self.tokenizers.get(name))
+                                 plans=plans, tokenizer=self.tokenizers.get(name),
+                                 kv_dtype=kw.get("kv_dtype"))
             svc = EngineService(pipe, name=f"{name.replace('/', '_')}-shards")
             self.shard_pipes[key] = svc
             return svc
@@ -656,6 +663,8 @@ def main(argv=None):
     ap.add_argument("--gpu", type=int, default=None, help="GPU index (implies USE_GPU=1)")
     ap.add_argument("--preload", default="", help="comma-separated models to load at start")
     ap.add_argument("--max-batch", type=int, default=None)
+    ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
+                    help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     ap.add_argument("--server", default="werkzeug", choices=["werkzeug", "uvicorn", "aiohttp"],
                     help="uvicorn: ASGI front (worker/asgi.py: /inference as a coroutine per "
                          "request) over the same Flask app; aiohttp: the same ASGI front on "
@@ -672,6 +681,9 @@ def main(argv=None):
             # current one, so nothing lands on device 0 by default
             torch.cuda.set_device(a.gpu)
     kw = {"max_batch": a.max_batch} if a.max_batch else None
+    if a.kv_dtype:
+        s.kv_cache_dtype = a.kv_dtype
+        kw = dict(kw or {}, kv_dtype=a.kv_dtype)
     app = create_worker_app(s, dev, kw)
     for m in [m for m in a.preload.split(",") if m]:
         app.extensions["dli_worker"].load_model(m)
