@@ -118,18 +118,36 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // MoE gate (moe.hip moe_route / moe_router kernels, fused_reduce.hip add + RMSNorm + gate):
-// softmax over the E logits (lane e < E holds logit e, the others -inf) -> top-k (HF: lowest
-// index on ties) -> renormalised weights; one wave per token
-__device__ __forceinline__ void route_pick(float x, int lane, int E, int k, int t,
-                                           float* __restrict__ topk_w,
-                                           int* __restrict__ topk_ids) {
-  const float mx = wave_max(x);
-  float p = lane < E ? __expf(x - mx) : 0.f;
-  const float s = wave_sum(p);
+// softmax over the E logits -> top-k (HF: lowest index on ties) -> weights p / sum(all),
+// divided by the sum of the picks when norm_topk (Mixtral; Qwen3-MoE's norm_topk_prob). One
+// wave per token; lane l holds the NR <= 4 experts e = l + 64 i in x[i] (E <= 64 NR; an expert
+// >= E holds -inf). NR is a compile-time count and every loop over it unrolls, so the logits
+// stay in NR registers (no indexed per-thread array). NR = 1 is the E <= 64 gate as it was:
+// the lane-local max / sum / argmax over one value are the value itself.
+template <int NR>
+__device__ __forceinline__ void route_pick_n(const float (&x)[NR], int lane, int E, int k, int t,
+                                             float* __restrict__ topk_w,
+                                             int* __restrict__ topk_ids, bool norm_topk) {
+  float lm = x[0];
+#pragma unroll
+  for (int i = 1; i < NR; ++i) lm = fmaxf(lm, x[i]);
+  const float mx = wave_max(lm);
+  float p[NR], ls = 0.f;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    p[i] = lane + 64 * i < E ? __expf(x[i] - mx) : 0.f;
+    ls = i == 0 ? p[0] : ls + p[i];
+  }
+  const float s = wave_sum(ls);
   float mine = 0.f, wsum = 0.f;                        // lane j keeps the j-th pick's weight
   for (int j = 0; j < k; ++j) {
-    float bv = lane < E ? p : -3.f;
+    float bv = lane < E ? p[0] : -3.f;
     int bi = lane;
+#pragma unroll
+    for (int i = 1; i < NR; ++i) {                     // the lane's own experts, ascending index
+      const float v = lane + 64 * i < E ? p[i] : -3.f;
+      if (v > bv) { bv = v; bi = lane + 64 * i; }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {                 // argmax, lowest index on ties (HF)
       const float ov = __shfl_xor(bv, o, 64);
@@ -139,9 +157,19 @@ __device__ __forceinline__ void route_pick(float x, int lane, int E, int k, int 
     const float w = bv / s;
     wsum += w;
     if (lane == j) { mine = w; topk_ids[t * k + j] = bi; }
-    if (lane == bi) p = -2.f;                          // taken
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      if (lane + 64 * i == bi) p[i] = -2.f;            // taken
   }
-  if (lane < k) topk_w[t * k + lane] = mine / wsum;
+  if (lane < k) topk_w[t * k + lane] = norm_topk ? mine / wsum : mine;
+}
+
+// the E <= 64 gate: lane e < E holds logit e, the others -inf
+__device__ __forceinline__ void route_pick(float x, int lane, int E, int k, int t,
+                                           float* __restrict__ topk_w,
+                                           int* __restrict__ topk_ids, bool norm_topk = true) {
+  const float xs[1] = {x};
+  route_pick_n<1>(xs, lane, E, k, t, topk_w, topk_ids, norm_topk);
 }
 
 

@@ -17,7 +17,9 @@
 //  * split-K over grid.y writes fp32 slabs; a second pass reduces and applies the epilogue.
 //  * grouped mode (MoE): grid.z = expert; rows of group g are [off[g], off[g+1]) of A/C,
 //    weights W + g*N*ldw. Rows past the group end are skipped. Split-K composes with it
-//    (slab rows are the permuted rows), for long-K expert GEMMs with few row tiles.
+//    (slab rows are the permuted rows), for long-K expert GEMMs with few row tiles. With many
+//    experts (Qwen3-MoE: 128) the generic tiles take the compact grid over the align step's
+//    list of non-empty row tiles instead (dli_gemm_grouped_list).
 // Epilogues: 0 bf16 store, 1 fp32 store (logits), 2 SiLU(gate)*up over the 16-row-interleaved
 // gate/up weight (output width N/2), 3 bias + tanh-GELU, 4 bias.
 //
@@ -50,19 +52,54 @@ extern "C" int dli_gemm_set_slab_store_family(int family, int mode) {
 // Grouped SiLU*up GEMM whose permuted row p reads activation row arow[p] (the MoE gate/up
 // projection without the gathered copy of its input rows): the generic tile family only,
 // unsplit. M: the row bound per group, as dli_gemm's grouped mode.
+static int grouped_gather(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M,
+                          int N, int K, int tile_cfg, const int* arow, const int* go, int groups,
+                          const int* tl, int tl_max, hipStream_t st) {
+  if (M <= 0 || N <= 0) return 0;
+  if (arow == nullptr || go == nullptr || groups < 1 || K % BK || lda % 8 || ldw % 8 || N % 32)
+    return (int)hipErrorInvalidValue;
+  const void* bias = arow;
+  void* ws = nullptr;
+  const int splits = 1;
+  const int r = gemm_tiles_dispatch(EPI_SILU, tile_cfg, DLI_GEMM_PASS);
+  return r == DLI_NOT_MINE ? (int)hipErrorInvalidValue : r;
+}
+
 extern "C" int dli_gemm_grouped_gather(const void* A, int lda, const void* W, int ldw, void* C,
                                        int ldc, int M, int N, int K, int tile_cfg,
                                        const int* arow, const int* group_off, int groups,
                                        hipStream_t st) {
-  if (M <= 0 || N <= 0) return 0;
-  if (arow == nullptr || group_off == nullptr || groups < 1 || K % BK || lda % 8 ||
-      ldw % 8 || N % 32)
+  return grouped_gather(A, lda, W, ldw, C, ldc, M, N, K, tile_cfg, arow, group_off, groups,
+                        nullptr, 0, st);
+}
+
+// The grouped GEMMs of the generic tile family on the compact grid: tile_list is what
+// dli_moe_align_tiles wrote for this tile's row height, max_items (>= ceil(M / BM) + groups)
+// the host-known bound on its item count that sizes the grid — (max_items x column tiles,
+// splits, 1) instead of (row tiles of M x column tiles, splits, groups). M: the total permuted
+// rows (the slab stride of a split call). arow non-null: the gather form (SiLU*up, unsplit);
+// else dli_gemm's grouped call (C null with splits > 1: the slabs alone).
+extern "C" int dli_gemm_grouped_list(const void* A, int lda, const void* W, int ldw, void* C,
+                                     int ldc, int M, int N, int K, int epi, int tile_cfg,
+                                     int splits, const int* arow, void* ws, const int* group_off,
+                                     int groups, const int* tile_list, int max_items,
+                                     hipStream_t st) {
+  if (tile_list == nullptr || group_off == nullptr || groups < 1)
     return (int)hipErrorInvalidValue;
-  const void* bias = arow;
-  void* ws = nullptr;
+  if (arow != nullptr) {
+    if (epi != EPI_SILU || splits != 1) return (int)hipErrorInvalidValue;
+    return grouped_gather(A, lda, W, ldw, C, ldc, M, N, K, tile_cfg, arow, group_off, groups,
+                          tile_list, max_items, st);
+  }
+  if (M <= 0 || N <= 0) return 0;
+  if (K % BK || lda % 8 || ldw % 8 || splits < 1 || (epi == EPI_SILU && N % 32) ||
+      (splits > 1 && ws == nullptr))
+    return (int)hipErrorInvalidValue;
+  const void* bias = nullptr;
   const int* go = group_off;
-  const int splits = 1;
-  const int r = gemm_tiles_dispatch(EPI_SILU, tile_cfg, DLI_GEMM_PASS);
+  const int* tl = tile_list;
+  const int tl_max = max_items;
+  const int r = gemm_tiles_dispatch(epi, tile_cfg, DLI_GEMM_PASS);
   return r == DLI_NOT_MINE ? (int)hipErrorInvalidValue : r;
 }
 
@@ -79,6 +116,8 @@ extern "C" int dli_gemm(const void* A, int lda, const void* W, int ldw, void* C,
   if (splits > 1 && ws == nullptr) return (int)hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   const int* go = group_off;
+  const int* tl = nullptr;
+  const int tl_max = 0;
   int r = gemm_tiles_dispatch(epi, tile_cfg, DLI_GEMM_PASS);
   if (r == DLI_NOT_MINE) r = gemm_8p_dispatch(epi, tile_cfg, DLI_GEMM_PASS);
   if (r == DLI_NOT_MINE) r = gemm_4w_dispatch(epi, tile_cfg, DLI_GEMM_PASS);

@@ -378,17 +378,47 @@ __device__ __forceinline__ void tile_origin(int tile, int tiles_m, int tiles_n, 
 // mode: grid.z = group, rows [off[g], off[g+1]), weights W + g N ldw; else the whole matrix,
 // M = max rows of any group), columns from n0, K-tiles [kb / BK, kb / BK + nk) of split ks.
 // A block with m0 >= Mg has nothing to do (block-uniform).
+// tile_list (grouped mode only, nullable): the compact grid (tiles x column tiles, splits, 1)
+// over the list moe_align_kernel wrote for this BM — pair 0 = (item count, BM), pair 1 + i =
+// (group, first row within the group) of item i. Workgroup t = blockIdx.x takes column tile
+// t % tiles_n of item t / tiles_n; at or past the count it has nothing to do. No XCD remap:
+// the items with work are the first of the grid, and the hardware's round-robin placement
+// (block L on XCD L % 8) spreads them over all eight XCDs, where the remap packs consecutive
+// tiles onto one (T = 1, 8 items: every working workgroup on XCD 0, the gate/up GEMM 52.6 us
+// against 32.6 us on the dense grid). The grid is sized by the host bound
+// ceil(rows / BM) + groups on the item count, not by M x groups. The tile a workgroup computes
+// is the one the dense grid's (m0, n0, blockIdx.z = group) workgroup computes.
 struct BlockCoord {
   int row0, Mg, m0, n0, kb, nk, ks;
   const u16* Wg;
 };
 template <int BM, int BN, int GM>
 __device__ __forceinline__ BlockCoord block_coord(const u16* W, int ldw, int M, int N, int K,
-                                                  int k_split_len, const int* group_off) {
+                                                  int k_split_len, const int* group_off,
+                                                  const int* tile_list = nullptr) {
   BlockCoord b;
   b.row0 = 0;
   b.Mg = M;
   b.Wg = W;
+  if (tile_list != nullptr) {
+    const int tiles_n = (N + BN - 1) / BN;
+    const int tile = blockIdx.x;
+    const int item = tile / tiles_n;
+    b.ks = blockIdx.y;
+    b.kb = b.ks * k_split_len;
+    b.nk = min(k_split_len, K - b.kb) / BK;
+    b.n0 = (tile - item * tiles_n) * BN;
+    b.m0 = 0;
+    b.Mg = 0;                                          // past the list: nothing to do
+    if (item < tile_list[0]) {
+      const int g = tile_list[2 + 2 * item];
+      b.m0 = tile_list[3 + 2 * item];
+      b.row0 = group_off[g];
+      b.Mg = group_off[g + 1] - b.row0;
+      b.Wg = W + (long)g * N * ldw;
+    }
+    return b;
+  }
   if (group_off != nullptr) {
     b.row0 = group_off[blockIdx.z];
     b.Mg = group_off[blockIdx.z + 1] - b.row0;
@@ -496,10 +526,12 @@ static __global__ void __launch_bounds__(256) splitk_reduce_kernel(void* __restr
 
 // the dispatch signature every family shares: (tile_cfg) -> that family's launcher, or
 // DLI_NOT_MINE when the tile id belongs to another family
+// tl / tl_max: the grouped tile list and the host bound on its item count (block_coord);
+// null / 0 everywhere but the generic tile family's list form
 #define DLI_GEMM_ARGS const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M, \
                       int N, int K, int splits, const void *bias, void *ws, const int *go,  \
-                      int groups, hipStream_t st
-#define DLI_GEMM_PASS A, lda, W, ldw, C, ldc, M, N, K, splits, bias, ws, go, groups, st
+                      int groups, const int *tl, int tl_max, hipStream_t st
+#define DLI_GEMM_PASS A, lda, W, ldw, C, ldc, M, N, K, splits, bias, ws, go, groups, tl, tl_max, st
 constexpr int DLI_NOT_MINE = -0x4d494e45;
 
 // The launcher of every kernel with the (A, lda, W, ldw, C, ldc, M, N, K, k_split_len, bias,
@@ -507,10 +539,15 @@ constexpr int DLI_NOT_MINE = -0x4d494e45;
 // dynamic LDS (> 64 KiB needs the opt-in, once per kernel), then the split-K reduce unless
 // C == nullptr (the partial slabs are left for a fused consumer, fused_reduce.hip). SILU_N:
 // the SiLU*up epilogue needs N to be a multiple of it; 0 = this tile has no SiLU epilogue
-// (a wave's column range does not hold whole gate/up pairs).
-template <auto KERNEL, int EPI, int BM, int BN, int THREADS, size_t LDS, int SILU_N>
+// (a wave's column range does not hold whole gate/up pairs). LIST: the kernel takes the tile
+// list as its last argument (grid (tl_max x column tiles, splits, 1) when one is given); the
+// other families refuse one.
+template <auto KERNEL, int EPI, int BM, int BN, int THREADS, size_t LDS, int SILU_N,
+          bool LIST = false>
 static int launch_gemm(DLI_GEMM_ARGS) {
   if (EPI == EPI_SILU && (SILU_N == 0 || N % (SILU_N ? SILU_N : 1)))
+    return (int)hipErrorInvalidValue;
+  if (tl != nullptr && (!LIST || go == nullptr || tl_max < (M + BM - 1) / BM + groups))
     return (int)hipErrorInvalidValue;
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   int ksl = K / splits;
@@ -523,9 +560,16 @@ static int launch_gemm(DLI_GEMM_ARGS) {
     if (e != hipSuccess) return (int)e;
     attr_done = true;
   }
-  KERNEL<<<dim3(tiles, splits, groups), THREADS, LDS, st>>>(
-      (const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K, ksl, (const u16*)bias, (float*)ws,
-      go);
+  if constexpr (LIST) {
+    const dim3 grid = tl != nullptr ? dim3(tl_max * ((N + BN - 1) / BN), splits, 1)
+                                    : dim3(tiles, splits, groups);
+    KERNEL<<<grid, THREADS, LDS, st>>>((const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K,
+                                       ksl, (const u16*)bias, (float*)ws, go, tl);
+  } else {
+    KERNEL<<<dim3(tiles, splits, groups), THREADS, LDS, st>>>(
+        (const u16*)A, lda, (const u16*)W, ldw, C, ldc, M, N, K, ksl, (const u16*)bias,
+        (float*)ws, go);
+  }
   if (splits > 1 && C != nullptr) {
     const int outN = (EPI == EPI_SILU) ? N / 2 : N;
     const long total = (long)M * outN;

@@ -1,6 +1,8 @@
 // Generic LDS-tiled MFMA GEMM family (family "tiles" of ops/gemm.py's TILE_TABLE, the one
 // list of tile ids; dispatch_tiles below is its C++ side): WM x WN waves, BM x BN x 64 block
-// tiles, 2 or 3 LDS stages filled by LDS-DMA. Split-K writes fp32 slabs for the fused
+// tiles, 2 or 3 LDS stages filled by LDS-DMA. Grouped (MoE) launches run on the dense grid
+// (row tiles x column tiles, splits, groups) or, given the align step's tile list, on the
+// compact grid over the non-empty row tiles (block_coord, gemm_common.h). Split-K writes fp32 slabs for the fused
 // consumers (fused_reduce.hip) or reduces them with splitk_reduce_kernel.
 #include "gemm_common.h"
 
@@ -8,7 +10,8 @@ template <int BM, int BN, int EPI, int NS, int WM, int WN, int STAG = 0>
 __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
     const u16* __restrict__ A, int lda, const u16* __restrict__ W, int ldw,
     void* __restrict__ C, int ldc, int M, int N, int K, int k_split_len,
-    const u16* __restrict__ bias, float* __restrict__ ws, const int* __restrict__ group_off) {
+    const u16* __restrict__ bias, float* __restrict__ ws, const int* __restrict__ group_off,
+    const int* __restrict__ tile_list) {
   constexpr int NW = WM * WN;                      // waves: WM along M x WN along N
   constexpr int TM = BM / WM, TN = BN / WN;        // wave tile
   constexpr int MI = TM / 16, NI = TN / 16;        // 16x16 MFMA blocks per wave
@@ -16,8 +19,9 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_bf16_kernel(
   constexpr int BUF = A_BYTES + W_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  // ---- tile coordinates (n-major tile order)
-  const BlockCoord bc = block_coord<BM, BN, 1>(W, ldw, M, N, K, k_split_len, group_off);
+  // ---- tile coordinates (n-major tile order; grouped with a tile list: the list's items)
+  const BlockCoord bc = block_coord<BM, BN, 1>(W, ldw, M, N, K, k_split_len, group_off,
+                                               tile_list);
   const int row0 = bc.row0, Mg = bc.Mg, m0 = bc.m0, n0 = bc.n0, kb = bc.kb, nk = bc.nk;
   const u16* Wg = bc.Wg;
   if (m0 >= Mg) return;                             // grouped: empty tile (block-uniform)
@@ -274,7 +278,8 @@ template <int BM, int BN, int EPI, int NS, int WM = 2, int WN = 2, int STAG = 0>
 static int launch_cfg(DLI_GEMM_ARGS) {
   // SiLU*up pairs gate/up blocks inside a wave's column range: a multiple of 32 columns
   return launch_gemm<gemm_bf16_kernel<BM, BN, EPI, NS, WM, WN, STAG>, EPI, BM, BN, 64 * WM * WN,
-                     NS * (size_t)(BM + BN) * BK * 2, (BN / WN) % 32 ? 0 : 32>(DLI_GEMM_PASS);
+                     NS * (size_t)(BM + BN) * BK * 2, (BN / WN) % 32 ? 0 : 32, true>(
+      DLI_GEMM_PASS);
 }
 
 template <int EPI>

@@ -1,23 +1,30 @@
 // Mixture-of-experts routing / permutation kernels (Mixtral) — SURVEY.md §2.4 K15/K16.
-//   route   : softmax over E router logits -> top-k -> renormalise (HF MixtralSparseMoeBlock)
-//   align   : per-expert counts, exclusive offsets, permuted position of every (token, slot)
+//   route   : softmax over E router logits -> top-k -> renormalise (HF MixtralSparseMoeBlock;
+//             Qwen3MoeSparseMoeBlock, which renormalises only with norm_topk_prob)
+//   align   : per-expert counts, exclusive offsets, permuted position of every (token, slot);
+//             optionally the list of non-empty row tiles for the grouped GEMMs' compact grid
 //   gather  : x_perm[p] = x[src[p]]            (16-B row copies)
 //   combine : out[t] = sum_slot w[t,slot] * y_perm[pos[t,slot]]   (fp32 sum, bf16 out)
 // The expert MLPs themselves run as grouped GEMMs (gemm.hip, grid.z = expert).
 #include "common.h"
 
-// One wave per token, lane e holds expert e (E <= 64): softmax max / sum and each of the k
-// argmax rounds are wave-wide shuffle reductions, so no per-thread logits array (the former
-// float p[64] per thread spilled to scratch).
+// One wave per token, lane l holds the experts l + 64 i, i < NR (E <= 64 NR): softmax max /
+// sum and each of the k argmax rounds are a lane-local pass over NR registers and a wave-wide
+// shuffle reduction, so no per-thread logits array (the former float p[64] per thread spilled
+// to scratch).
+template <int NR>
 __global__ void __launch_bounds__(256) moe_route_kernel(float* __restrict__ topk_w,
                                                         int* __restrict__ topk_ids,
                                                         const u16* __restrict__ logits, int T,
-                                                        int E, int k) {
+                                                        int E, int k, bool norm_topk) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;                                  // wave-uniform
-  const float x = lane < E ? bf2f(logits[(long)t * E + lane]) : -INFINITY;
-  route_pick(x, lane, E, k, t, topk_w, topk_ids);
+  float x[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i)
+    x[i] = lane + 64 * i < E ? bf2f(logits[(long)t * E + lane + 64 * i]) : -INFINITY;
+  route_pick_n<NR>(x, lane, E, k, t, topk_w, topk_ids, norm_topk);
 }
 
 // The Mixtral gate in one pass: the E <= 8 router logits of a token are dot products of its
@@ -107,11 +114,20 @@ extern "C" int dli_moe_router(float* topk_w, int* topk_ids, const void* h, int l
   DLI_RETURN_LAUNCH();
 }
 
+// E <= 64: any k <= E (lane j keeps the j-th pick); 64 < E <= 256: k <= 8
 extern "C" int dli_moe_route(float* topk_w, int* topk_ids, const void* logits, int T, int E, int k,
-                             hipStream_t st) {
+                             int norm_topk, hipStream_t st) {
   if (T <= 0) return 0;
-  if (E > 64 || k > E) return (int)hipErrorInvalidValue;
-  moe_route_kernel<<<(T + 3) / 4, 256, 0, st>>>(topk_w, topk_ids, (const u16*)logits, T, E, k);
+  if (E < 1 || E > 256 || k < 1 || k > E || (E > 64 && k > 8)) return (int)hipErrorInvalidValue;
+#define DLI_ROUTE(NR) moe_route_kernel<NR><<<(T + 3) / 4, 256, 0, st>>>(                  \
+      topk_w, topk_ids, (const u16*)logits, T, E, k, norm_topk != 0)
+  switch ((E + 63) / 64) {
+    case 1: DLI_ROUTE(1); break;
+    case 2: DLI_ROUTE(2); break;
+    case 3: DLI_ROUTE(3); break;
+    default: DLI_ROUTE(4); break;
+  }
+#undef DLI_ROUTE
   DLI_RETURN_LAUNCH();
 }
 
@@ -119,13 +135,26 @@ extern "C" int dli_moe_route(float* topk_w, int* topk_ids, const void* logits, i
 // block-strided, LDS atomics; the expert-offset scan is one wave's shuffle scan). ids: [n]
 // expert ids; experts outside [e0, e0+E_local) are dropped (pos = -1). offsets:
 // [E_local + 1]; pos: [n]; src: [n] (token of each permuted row).
+// tl (nullable): the work lists of the grouped GEMMs' compact grid (gemm_common.h
+// block_coord), one per row-tile height in use (the gate/up and the down projection may run
+// different tiles). A list for tiles of bm rows is int pairs: pair 0 = (item count, bm), pair
+// 1 + i = item i = (local expert, first row within the expert), one for every bm rows of
+// every non-empty expert, experts ascending. count <= ceil(n / bm) + E_local <= max_items (a
+// non-empty expert adds at most one partial tile); no item is written past max_items.
+struct MoeTileLists {
+  int* list[2];                                        // null: unused
+  int bm[2], max_items[2];
+};
+
 __global__ void __launch_bounds__(1024) moe_align_kernel(int* __restrict__ offsets,
                                                          int* __restrict__ pos,
                                                          int* __restrict__ src,
                                                          const int* __restrict__ ids, int n,
-                                                         int k, int e0, int E_local) {
+                                                         int k, int e0, int E_local,
+                                                         MoeTileLists tl) {
   __shared__ int cnt[256];
   __shared__ int off[257];
+  __shared__ int toff[257];                            // first item of each expert
   for (int i = threadIdx.x; i < E_local; i += blockDim.x) cnt[i] = 0;
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -151,6 +180,40 @@ __global__ void __launch_bounds__(1024) moe_align_kernel(int* __restrict__ offse
     if (lane == 0) off[E_local] = run;
   }
   __syncthreads();
+#pragma unroll
+  for (int l = 0; l < 2; ++l) {
+    if (tl.list[l] == nullptr) continue;               // uniform
+    const int bm = tl.bm[l], cap = tl.max_items[l];
+    if (threadIdx.x < 64) {                            // the same scan over the row-tile counts
+      const int lane = threadIdx.x;
+      int run = 0;
+      for (int base = 0; base < E_local; base += 64) {
+        const int e = base + lane;
+        const int c = e < E_local ? (off[e + 1] - off[e] + bm - 1) / bm : 0;
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int y = __shfl_up(incl, o, 64);
+          if (lane >= o) incl += y;
+        }
+        if (e < E_local) toff[e] = run + incl - c;
+        run += __shfl(incl, 63, 64);
+      }
+      if (lane == 0) {
+        tl.list[l][0] = min(run, cap);
+        tl.list[l][1] = bm;
+      }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < E_local; e += blockDim.x) {
+      const int rows = off[e + 1] - off[e];
+      for (int r = 0, it = toff[e]; r < rows && it < cap; r += bm, ++it) {
+        tl.list[l][2 + 2 * it] = e;
+        tl.list[l][3 + 2 * it] = r;
+      }
+    }
+    __syncthreads();                                   // toff is reused by the next list
+  }
   for (int e = threadIdx.x; e <= E_local; e += blockDim.x) {
     offsets[e] = off[e];
     if (e < E_local) cnt[e] = 0;
@@ -171,7 +234,23 @@ __global__ void __launch_bounds__(1024) moe_align_kernel(int* __restrict__ offse
 extern "C" int dli_moe_align(int* offsets, int* pos, int* src, const int* ids, int n, int k,
                              int e0, int E_local, hipStream_t st) {
   if (E_local > 256) return (int)hipErrorInvalidValue;
-  moe_align_kernel<<<1, 1024, 0, st>>>(offsets, pos, src, ids, n, k, e0, E_local);
+  moe_align_kernel<<<1, 1024, 0, st>>>(offsets, pos, src, ids, n, k, e0, E_local,
+                                       MoeTileLists{});
+  DLI_RETURN_LAUNCH();
+}
+
+// the align plus the tile lists for row tiles of bm_a (and, list_b non-null, bm_b) rows: a
+// list holds 2 (1 + max_items) ints, max_items >= ceil(n / bm) + E_local
+extern "C" int dli_moe_align_tiles(int* offsets, int* pos, int* src, const int* ids, int n, int k,
+                                   int e0, int E_local, int* list_a, int bm_a, int max_a,
+                                   int* list_b, int bm_b, int max_b, hipStream_t st) {
+  if (E_local > 256 || list_a == nullptr || bm_a < 1 || max_a < (n + bm_a - 1) / bm_a + E_local ||
+      (list_b != nullptr && (bm_b < 1 || max_b < (n + bm_b - 1) / bm_b + E_local)))
+    return (int)hipErrorInvalidValue;
+  MoeTileLists tl{};
+  tl.list[0] = list_a; tl.bm[0] = bm_a; tl.max_items[0] = max_a;
+  tl.list[1] = list_b; tl.bm[1] = bm_b; tl.max_items[1] = max_b;
+  moe_align_kernel<<<1, 1024, 0, st>>>(offsets, pos, src, ids, n, k, e0, E_local, tl);
   DLI_RETURN_LAUNCH();
 }
 
@@ -271,13 +350,13 @@ __global__ void __launch_bounds__(256) moe_combine_slabs_kernel(
 }
 
 // The combine above, then the next layer's input norm in the same pass (one workgroup per
-// token, 512 threads x 8 columns = dim 4096): m = bf16(sum_j w_j bf16(sum_s P_s[pos_j]))
+// token, THREADS x 8 columns = dim: 512 for 4096, 256 for 2048): m = bf16(sum_j w_j bf16(sum_s P_s[pos_j]))
 // (what moe_combine_slabs_kernel stores), residual = bf16(residual + m), out =
 // rmsnorm(residual) * nw — the combine's bf16 output and the separate add + RMSNorm kernel
 // (norm_kernel, 7.5 us per layer at batch 512) go away. nw null: the residual add only (a
 // stage's last layer).
-template <int S>
-__global__ void __launch_bounds__(512) moe_combine_add_rmsnorm_kernel(
+template <int S, int THREADS>
+__global__ void __launch_bounds__(THREADS) moe_combine_add_rmsnorm_kernel(
     u16* __restrict__ out, u16* __restrict__ residual, const u16* __restrict__ ws,
     long slab_stride, const float* __restrict__ w, const int* __restrict__ pos, int k, int dim,
     const u16* __restrict__ nw, float eps) {
@@ -308,10 +387,11 @@ extern "C" int dli_moe_combine_add_rmsnorm(void* out, void* residual, const void
                                            int k, int dim, const void* nw, float eps,
                                            hipStream_t st) {
   if (T <= 0) return 0;
-  if (dim != 4096) return (int)hipErrorInvalidValue;
+  if (dim != 4096 && dim != 2048) return (int)hipErrorInvalidValue;
   const long stride = (long)rows * dim;
-#define DLI_MCN(S) moe_combine_add_rmsnorm_kernel<S><<<T, 512, 0, st>>>(                   \
+#define DLI_MCN_T(S, TH) moe_combine_add_rmsnorm_kernel<S, TH><<<T, TH, 0, st>>>(          \
       (u16*)out, (u16*)residual, (const u16*)ws, stride, w, pos, k, dim, (const u16*)nw, eps)
+#define DLI_MCN(S) if (dim == 4096) DLI_MCN_T(S, 512); else DLI_MCN_T(S, 256)
   switch (splits) {
     case 2: DLI_MCN(2); break;
     case 4: DLI_MCN(4); break;
@@ -319,6 +399,7 @@ extern "C" int dli_moe_combine_add_rmsnorm(void* out, void* residual, const void
     default: return (int)hipErrorInvalidValue;
   }
 #undef DLI_MCN
+#undef DLI_MCN_T
   DLI_RETURN_LAUNCH();
 }
 

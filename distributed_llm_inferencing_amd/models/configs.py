@@ -42,6 +42,9 @@ class ModelConfig:
     # query and key head before RoPE; Qwen2 / 2.5: a bias on the fused QKV projection (bqkv)
     qk_norm: bool = False
     qkv_bias: bool = False
+    # MoE routing weights: True (Mixtral; the released Qwen3-MoE checkpoints) divides the top-k
+    # softmax probabilities by their sum, False (Qwen3MoeConfig's default) keeps them as they are
+    norm_topk_prob: bool = True
 
     @property
     def is_moe(self) -> bool:
@@ -143,6 +146,13 @@ QWEN25_7B = ModelConfig(
     max_position=131072, rope_theta=1e6, norm_eps=1e-6, bos_token_id=151643,
     eos_token_id=151643, qkv_bias=True)
 
+# Qwen3-30B-A3B: Qwen3 layers with 128 experts of width 768 (moe_intermediate_size), top-8
+QWEN3_30B_A3B = ModelConfig(
+    name="qwen3-30b-a3b", arch="llama", hidden_size=2048, num_layers=48, num_heads=32,
+    num_kv_heads=4, head_dim=128, intermediate_size=768, vocab_size=151936, max_position=40960,
+    rope_theta=1e6, norm_eps=1e-6, num_experts=128, top_k_experts=8, bos_token_id=151643,
+    eos_token_id=151645, qk_norm=True, norm_topk_prob=True)
+
 # Tiny variants: same code paths, test-sized. Shapes keep the hardware-friendly
 # multiples (head_dim 64/128, hidden multiple of 256) so HIP kernels see real layouts.
 LLAMA_TINY = ModelConfig(
@@ -173,6 +183,13 @@ MIXTRAL_TINY = replace(LLAMA_TINY, name="mixtral-tiny", num_experts=4, top_k_exp
 # 8 experts: one per rank of an 8-rank expert-parallel test
 MIXTRAL_TINY8E = replace(MIXTRAL_TINY, name="mixtral-tiny8e", num_experts=8)
 
+# Qwen3-MoE twins: 128 experts / top-8 (more than a wave's lanes, the compact tile list of
+# the grouped GEMMs); 16 experts / top-4 with un-renormalised routing weights
+QWEN3_MOE_TINY = replace(QWEN3_TINY, name="qwen3-moe-tiny", num_experts=128, top_k_experts=8,
+                         intermediate_size=64)
+QWEN3_MOE_TINY128 = replace(QWEN3_TINY128, name="qwen3-moe-tiny128", num_experts=16,
+                            top_k_experts=4, intermediate_size=128, norm_topk_prob=False)
+
 GPT2_TINY = replace(GPT2, name="gpt2-tiny", hidden_size=256, num_layers=2, num_heads=4,
                     num_kv_heads=4, head_dim=64, intermediate_size=1024, vocab_size=1024,
                     max_position=256, bos_token_id=1023, eos_token_id=1023)
@@ -180,7 +197,8 @@ GPT2_TINY = replace(GPT2, name="gpt2-tiny", hidden_size=256, num_layers=2, num_h
 _REGISTRY = {c.name: c for c in
              (GPT2, LLAMA3_8B, LLAMA3_70B, MIXTRAL_8X7B, LLAMA_TINY, LLAMA_TINY128,
               LLAMA_TINY8, MIXTRAL_TINY, MIXTRAL_TINY8E, GPT2_TINY, MISTRAL_7B, MISTRAL_TINY,
-              MISTRAL_TINY128, QWEN3_8B, QWEN25_7B, QWEN3_TINY, QWEN3_TINY128, QWEN2_TINY128)}
+              MISTRAL_TINY128, QWEN3_8B, QWEN25_7B, QWEN3_TINY, QWEN3_TINY128, QWEN2_TINY128,
+              QWEN3_30B_A3B, QWEN3_MOE_TINY, QWEN3_MOE_TINY128)}
 
 _ALIASES = {
     "openai-community/gpt2": "gpt2",
@@ -200,6 +218,8 @@ _ALIASES = {
     "qwen/qwen3-8b": "qwen3-8b",
     "qwen/qwen2.5-7b": "qwen2.5-7b",
     "qwen/qwen2.5-7b-instruct": "qwen2.5-7b",
+    "qwen/qwen3-30b-a3b": "qwen3-30b-a3b",
+    "qwen3_30b_a3b": "qwen3-30b-a3b",
 }
 
 

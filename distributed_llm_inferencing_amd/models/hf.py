@@ -1,6 +1,6 @@
 """HF checkpoint import: ``save_pretrained`` directories (and hub-cache snapshots) of
 LlamaForCausalLM / MistralForCausalLM / MixtralForCausalLM / Qwen2ForCausalLM /
-Qwen3ForCausalLM / GPT2LMHeadModel.
+Qwen3ForCausalLM / Qwen3MoeForCausalLM / GPT2LMHeadModel.
 
 The reference loads checkpoints with ``AutoModelForCausalLM.from_pretrained(model_name,
 cache_dir=MODEL_CACHE_DIR)`` (``worker/app.py:117-124``) and its sharder shards a loaded HF
@@ -61,8 +61,10 @@ def find_hf_dir(root: str, name: str) -> Optional[Path]:
 
 def config_from_hf(c: dict, name: Optional[str] = None,
                    sliding_window: bool = False) -> ModelConfig:
-    """Map a HF ``config.json`` (llama / mistral / mixtral / qwen2 / qwen3 / gpt2 model types;
-    qwen3 sets ``qk_norm``, qwen2 — and a qwen3 with ``attention_bias`` — ``qkv_bias``).
+    """Map a HF ``config.json`` (llama / mistral / mixtral / qwen2 / qwen3 / qwen3_moe / gpt2
+    model types; qwen3 and qwen3_moe set ``qk_norm``, qwen2 — and a qwen3 / qwen3_moe with
+    ``attention_bias`` — ``qkv_bias``). qwen3_moe: every layer sparse, no shared expert; the
+    expert width is ``moe_intermediate_size`` and an absent ``norm_topk_prob`` means false.
     ``sliding_window``: the caller runs the model through ``TransformerLM``, whose attention
     honours ``ModelConfig.sliding_window``: a checkpoint's window (smaller than its
     ``max_position_embeddings``) is kept and the context is the model's own. Without it the
@@ -79,15 +81,35 @@ def config_from_hf(c: dict, name: Optional[str] = None,
             rope_theta=0.0, norm_eps=float(c.get("layer_norm_epsilon", 1e-5)),
             tie_embeddings=True, bos_token_id=int(c.get("bos_token_id", 50256)),
             eos_token_id=_eos(c, 50256))
-    if mt not in ("llama", "mistral", "mixtral", "qwen2", "qwen3"):
+    if mt not in ("llama", "mistral", "mixtral", "qwen2", "qwen3", "qwen3_moe"):
         raise ValueError(f"unsupported HF model_type '{mt}' "
-                         "(llama, mistral, mixtral, qwen2, qwen3, gpt2)")
-    qwen = mt in ("qwen2", "qwen3")
+                         "(llama, mistral, mixtral, qwen2, qwen3, qwen3_moe, gpt2)")
+    qwen = mt in ("qwen2", "qwen3", "qwen3_moe")
     if qwen and c.get("use_sliding_window"):
         raise ValueError(
             f"{mt} checkpoint with use_sliding_window=true: it windows only some of its layers "
             "(max_window_layers / layer_types), and this engine applies one window to every "
             "layer")
+    experts, inter, norm_topk = 0, c.get("intermediate_size"), True
+    if mt == "mixtral":
+        experts = int(c.get("num_local_experts", 0))
+    elif mt == "qwen3_moe":
+        # this engine runs one kind of layer: every layer sparse, routed experts only
+        if c.get("mlp_only_layers"):
+            raise ValueError(f"qwen3_moe checkpoint with mlp_only_layers={c['mlp_only_layers']}: "
+                             "dense and sparse layers cannot be mixed")
+        if int(c.get("decoder_sparse_step", 1)) != 1:
+            raise ValueError(f"qwen3_moe checkpoint with decoder_sparse_step="
+                             f"{c['decoder_sparse_step']}: every layer must be sparse (1)")
+        for f in ("shared_expert_intermediate_size", "num_shared_experts"):
+            if c.get(f):
+                raise ValueError(f"qwen3_moe checkpoint with {f}={c[f]}: shared experts "
+                                 "(Qwen2-MoE) are not supported")
+        experts = int(c.get("num_experts") or c.get("num_local_experts") or 0)
+        if experts <= 0:
+            raise ValueError("qwen3_moe checkpoint without num_experts")
+        inter = c["moe_intermediate_size"]
+        norm_topk = bool(c.get("norm_topk_prob", False))
     d, nh = int(c["hidden_size"]), int(c["num_attention_heads"])
     rope = c.get("rope_theta")
     params = c.get("rope_parameters") or {}
@@ -124,17 +146,19 @@ def config_from_hf(c: dict, name: Optional[str] = None,
         name=name, arch="llama", hidden_size=d, num_layers=int(c["num_hidden_layers"]),
         num_heads=nh, num_kv_heads=int(c.get("num_key_value_heads") or nh),
         head_dim=int(c.get("head_dim") or d // nh),
-        intermediate_size=int(c["intermediate_size"]), vocab_size=int(c["vocab_size"]),
+        intermediate_size=int(inter), vocab_size=int(c["vocab_size"]),
         max_position=max_pos, rope_theta=float(rope),
         rope_scaling=tuple(sorted((str(k), v) for k, v in sc.items()
                                   if isinstance(v, (int, float, str)))),
         norm_eps=float(c.get("rms_norm_eps", 1e-5)),
-        num_experts=int(c.get("num_local_experts", 0)) if mt == "mixtral" else 0,
+        num_experts=experts,
         top_k_experts=int(c.get("num_experts_per_tok", 2)),
         tie_embeddings=bool(c.get("tie_word_embeddings", False)),
         bos_token_id=int(c.get("bos_token_id") or 1), eos_token_id=_eos(c, 2),
-        sliding_window=window, qk_norm=mt == "qwen3",
-        qkv_bias=mt == "qwen2" or (mt == "qwen3" and bool(c.get("attention_bias", False))))
+        sliding_window=window, qk_norm=mt in ("qwen3", "qwen3_moe"),
+        qkv_bias=mt == "qwen2" or (mt in ("qwen3", "qwen3_moe")
+                                   and bool(c.get("attention_bias", False))),
+        norm_topk_prob=norm_topk)
 
 
 def _eos(c: dict, default: int) -> int:

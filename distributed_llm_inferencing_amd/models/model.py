@@ -175,7 +175,8 @@ class TransformerLM:
                 # kernel when the slabs allow: ops.linear_add_rmsnorm route)
                 h, tw, ti = ops.linear_add_rmsnorm(attn, lp["wo"], residual, lp["mlp_norm"],
                                                    eps, route=(lp["router"],
-                                                               cfg.top_k_experts))
+                                                               cfg.top_k_experts,
+                                                               cfg.norm_topk_prob))
                 pending = self.moe_fn(h, lp, self.layer_start + li, (tw, ti))
                 continue
             h = self._proj_add_norm(attn, lp["wo"], residual, lp["mlp_norm"], eps, defer)
@@ -255,7 +256,8 @@ class TransformerLM:
         projection's reduce, ``_llama_layers``) a decode step returns an ``ops.MoEPending``:
         its combine runs inside the next layer's add + RMSNorm."""
         topk_w, topk_ids = (routing if routing is not None
-                            else ops.moe_router(h, lp["router"], self.cfg.top_k_experts))
+                            else ops.moe_router(h, lp["router"], self.cfg.top_k_experts,
+                                                self.cfg.norm_topk_prob))
         e0 = self.expert_range[0] if self.expert_range else 0
         return ops.moe_mlp(h, lp["w_gu"], lp["w_down"], topk_w, topk_ids, e0,
                            defer_combine=routing is not None)

@@ -109,7 +109,7 @@ class MoEPending:
     def add_rmsnorm(self, residual, w, eps):
         """w None: the residual add only (a stage's last layer); returns None then."""
         T, D = self.shape
-        if D != 4096 or not residual.is_contiguous():
+        if D not in (4096, 2048) or not residual.is_contiguous():
             m = self.materialize()
             if w is None:
                 residual.add_(m)
@@ -213,7 +213,11 @@ def embedding(ids, table, pos_table=None, positions=None):
 
 # ----------------------------------------------------------------------------- GEMM
 def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan] = None,
-                 groups: int = 1, group_off=None, rows_per_group: Optional[int] = None):
+                 groups: int = 1, group_off=None, rows_per_group: Optional[int] = None,
+                 tile_list=None):
+    """``tile_list`` = (list, max items) of a grouped call: the compact grid over the align
+    step's list for the plan's tile height (``dli_gemm_grouped_list``); ``rows_per_group`` is
+    then the total permuted rows."""
     M, K = x.shape
     Nn = w.shape[-2]
     if plan is None:
@@ -230,6 +234,11 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
     if splits > 1:
         ws = G.workspace(x.device, splits * M * Nn * 4)
     m_arg = M if group_off is None else rows_per_group
+    if tile_list is not None:
+        _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), _p(out),
+                     out.stride(0), m_arg, Nn, K, G.EPI[epi], plan.tile, splits, None, _p(ws),
+                     _p(group_off), groups, _p(tile_list[0]), tile_list[1], _st())
+        return out
     _native_call("dli_gemm", _p(x), x.stride(0), _p(w), w.stride(-2), _p(out), out.stride(0),
                  m_arg, Nn, K, G.EPI[epi], plan.tile, splits, _p(bias), _p(ws), _p(group_off),
                  groups, _st())
@@ -295,16 +304,18 @@ def linear_add_rmsnorm(x, w, residual, norm_w, eps, plan: Optional[G.GemmPlan] =
     (None when norm_w is None). Split-K GEMMs reduce their partial slabs inside the norm
     kernel (fused_reduce.hip), so the bf16 GEMM output is never materialised.
     ``plan`` forces the GEMM plan (the autotuner times every candidate with its consumer).
-    ``route`` = (router weight [E, N], k): also the MoE gate of the output rows — returns
-    (out, topk_w, topk_ids); with fp16 slabs, N = 4096 and E <= 8 inside the same reduce
-    kernel (``dli_splitk_add_rmsnorm_route``), else by ``moe_router``."""
+    ``route`` = (router weight [E, N], k[, norm_topk = True]): also the MoE gate of the output
+    rows — returns (out, topk_w, topk_ids); with fp16 slabs, N = 4096, E <= 8 and renormalised
+    weights inside the same reduce kernel (``dli_splitk_add_rmsnorm_route``), else by
+    ``moe_router``."""
     if route is not None:
-        wr, k = route
+        wr, k = route[:2]
+        norm_topk = route[2] if len(route) > 2 else True
         p = _splitk_plan(x, w) if plan is None else (plan if plan.splits > 1 else None)
         M, K = x.shape
         Nn = w.shape[0]
         if (p is not None and norm_w is not None and Nn == 4096 and wr.shape[0] <= 8
-                and wr.is_contiguous() and residual.is_contiguous()
+                and norm_topk and wr.is_contiguous() and residual.is_contiguous()
                 and wr.data_ptr() % 16 == 0):
             ws = G.workspace(x.device, p.splits * M * Nn * 4)
             fmt = _slab_gemm(x, w, p, ws)
@@ -321,7 +332,7 @@ def linear_add_rmsnorm(x, w, residual, norm_w, eps, plan: Optional[G.GemmPlan] =
                          Nn, _p(norm_w), eps, fmt, _st())
         else:
             out = linear_add_rmsnorm(x, w, residual, norm_w, eps, plan=plan)
-        return (out,) + tuple(moe_router(out, wr, k))
+        return (out,) + tuple(moe_router(out, wr, k, norm_topk))
     if plan is None:
         p = _splitk_plan(x, w)
     else:
@@ -799,23 +810,27 @@ def head_candidates(h, w_slice, offset: int, c: int):
 
 
 # ----------------------------------------------------------------------------- MoE
-def moe_route(router_logits, k: int):
+def moe_route(router_logits, k: int, norm_topk: bool = True):
+    """softmax -> top-``k`` (lowest index on ties) -> weights p / sum(all), divided by the sum
+    of the picks when ``norm_topk``; up to 256 experts, k <= 8 past 64 (``moe_route_kernel``)."""
     if not _use_native(router_logits):
-        return R.router_topk(router_logits, k)
+        return R.router_topk(router_logits, k, norm_topk)
     T, E = router_logits.shape
     w = torch.empty(T, k, dtype=torch.float32, device=router_logits.device)
     ids = torch.empty(T, k, dtype=torch.int32, device=router_logits.device)
-    _native_call("dli_moe_route", _p(w), _p(ids), _p(router_logits), T, E, k, _st())
+    _native_call("dli_moe_route", _p(w), _p(ids), _p(router_logits), T, E, k, int(norm_topk),
+                 _st())
     return w, ids
 
 
-def moe_router(h, w_router, k: int):
+def moe_router(h, w_router, k: int, norm_topk: bool = True):
     """The MoE gate: logits = h @ w_router.T (bf16, as a GEMM would write them), softmax,
-    top-``k``, renormalised. On the GPU with <= 8 experts one kernel does all of it
-    (``moe_router_kernel``, a wave per token); else the GEMM then ``moe_route``."""
+    top-``k``, renormalised when ``norm_topk``. On the GPU with <= 8 experts and renormalised
+    weights one kernel does all of it (``moe_router_kernel``, a workgroup per token); else the
+    GEMM then ``moe_route``."""
     T, D = h.shape
     E = w_router.shape[0]
-    if (_use_native(h) and E <= 8 and D % 8 == 0 and h.stride(-1) == 1
+    if (_use_native(h) and E <= 8 and norm_topk and D % 8 == 0 and h.stride(-1) == 1
             and h.stride(0) % 8 == 0 and w_router.is_contiguous()
             and h.data_ptr() % 16 == 0 and w_router.data_ptr() % 16 == 0):
         w = torch.empty(T, k, dtype=torch.float32, device=h.device)
@@ -823,7 +838,7 @@ def moe_router(h, w_router, k: int):
         _native_call("dli_moe_router", _p(w), _p(ids), _p(h), h.stride(0), _p(w_router), T, E,
                      D, k, _st())
         return w, ids
-    return moe_route(linear(h, w_router), k)
+    return moe_route(linear(h, w_router), k, norm_topk)
 
 
 def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
@@ -834,7 +849,10 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     sized for the worst case (the expert-parallel receive region: every peer's bucket at
     min(k, E/N) rows per token). The grouped-GEMM plan is looked up for it — the autotuned
     key — instead of for the capacity, whose 4-8x larger row count mapped to 256-row tiles
-    (1 workgroup per CU) that streamed the experts at ~2 TB/s."""
+    (1 workgroup per CU) that streamed the experts at ~2 TB/s.
+    With more than ``G.LIST_MIN_GROUPS`` local experts (Qwen3-MoE) the grouped GEMMs of the
+    generic tile family run on the compact grid over the align step's tile list
+    (``G.list_plan``), whose size does not grow as rows x experts."""
     if not _use_native(x):
         return R.moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset)
     T, D = x.shape
@@ -845,10 +863,31 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     offsets = torch.empty(E_local + 1, dtype=torch.int32, device=dev)
     pos = torch.empty(n, dtype=torch.int32, device=dev)
     src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    _native_call("dli_moe_align", _p(offsets), _p(pos), _p(src), _p(topk_ids), n, k,
-                 expert_offset, E_local, _st())
+    prefill = (n >= _MOE_PREFILL_ROWS * E_local
+               and not torch.cuda.is_current_stream_capturing())
+    rows = plan_rows if plan_rows is not None else n
+    p_gu = G.grouped_plan(rows, F2, D, "silu_mul", E_local)
+    p_dn = G.grouped_plan(rows, D, F2 // 2, "none", E_local)
+    # one tile list per row-tile height that the two projections run on the compact grid
+    lists = {}
+    if not prefill and n > 0:
+        for p in (p_gu, p_dn):
+            bm = G.TILES[p.tile][0]
+            if G.list_plan(p, E_local) and bm not in lists:
+                cap = G.max_items(n, E_local, bm)
+                lists[bm] = (torch.empty(1 + cap, 2, dtype=torch.int32, device=dev), cap)
+    if lists:
+        a, b = (list(lists.items()) + [(0, (None, 0))])[:2]      # (bm, (list, max items))
+        _native_call("dli_moe_align_tiles", _p(offsets), _p(pos), _p(src), _p(topk_ids), n, k,
+                     expert_offset, E_local, _p(a[1][0]), a[0], a[1][1], _p(b[1][0]), b[0],
+                     b[1][1], _st())
+    else:
+        _native_call("dli_moe_align", _p(offsets), _p(pos), _p(src), _p(topk_ids), n, k,
+                     expert_offset, E_local, _st())
+    tl_gu = lists.get(G.TILES[p_gu.tile][0]) if G.list_plan(p_gu, E_local) else None
+    tl_dn = lists.get(G.TILES[p_dn.tile][0]) if G.list_plan(p_dn, E_local) else None
     act = torch.empty(max(n, 1), F2 // 2, dtype=x.dtype, device=dev)
-    if n >= _MOE_PREFILL_ROWS * E_local and not torch.cuda.is_current_stream_capturing():
+    if prefill:
         # prefill-sized expert GEMMs (thousands of rows per expert) are compute-bound: a
         # grouped 256x256 kernel (G.MOE_PREFILL_TILE: the two-barrier 4-wave tile, grid.z =
         # expert) with the fused SiLU*up epilogue. The largest expert's row count bounds the
@@ -869,36 +908,36 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
         out = torch.empty_like(x)
         _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
         return out
-    rows = plan_rows if plan_rows is not None else n
-    p_gu = G.grouped_plan(rows, F2, D, "silu_mul", E_local)
     if p_gu.splits == 1 and p_gu.tile in G.GATHER_TILES and x.is_contiguous():
         # the gate/up GEMM reads the token rows in place through the permutation (no gathered
         # copy of them: dli_gemm_grouped_gather, the generic tile family)
-        _native_call("dli_gemm_grouped_gather", _p(x), x.stride(0), _p(w_gu), w_gu.stride(-2),
-                     _p(act), act.stride(0), n, F2, D, p_gu.tile, _p(src), _p(offsets),
-                     E_local, _st())
+        if tl_gu is not None:
+            _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w_gu),
+                         w_gu.stride(-2), _p(act), act.stride(0), n, F2, D,
+                         G.EPI["silu_mul"], p_gu.tile, 1, _p(src), None, _p(offsets), E_local,
+                         _p(tl_gu[0]), tl_gu[1], _st())
+        else:
+            _native_call("dli_gemm_grouped_gather", _p(x), x.stride(0), _p(w_gu),
+                         w_gu.stride(-2), _p(act), act.stride(0), n, F2, D, p_gu.tile, _p(src),
+                         _p(offsets), E_local, _st())
     else:
         # permuted rows: at most n (all local); rows past offsets[E_local] are never touched
         xp = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
         _native_call("dli_moe_gather", _p(xp), _p(x), _p(src), n, D, _p(offsets[E_local:]),
                      _st())
         _gemm_native(xp, w_gu, "silu_mul", out=act, groups=E_local, group_off=offsets,
-                     rows_per_group=n, plan=p_gu)
-    p_dn = G.grouped_plan(rows, D, F2 // 2, "none", E_local)
+                     rows_per_group=n, plan=p_gu, tile_list=tl_gu)
     if moe_slab_plan(p_dn):
         if defer_combine:
             # the down projection's slabs; the combine runs with the next layer's add + norm
-            ws = G.workspace(dev, p_dn.splits * max(n, 1) * D * 2)
-            _native_call("dli_gemm", _p(act), act.stride(0), _p(w_down), w_down.stride(-2),
-                         None, D, n, D, F2 // 2, G.EPI["slab16"], p_dn.tile, p_dn.splits, None,
-                         _p(ws), _p(offsets), E_local, _st())
+            ws = _moe_down_slabs(act, w_down, offsets, n, p_dn, tl_dn)
             return MoEPending(ws, p_dn.splits, n, topk_w, pos, (T, D), x.dtype, dev)
         out = torch.empty_like(x)
-        moe_down_combine(act, w_down, offsets, n, p_dn, topk_w, pos, out)
+        moe_down_combine(act, w_down, offsets, n, p_dn, topk_w, pos, out, tile_list=tl_dn)
         return out
     y = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
     _gemm_native(act, w_down, "none", out=y, groups=E_local, group_off=offsets,
-                 rows_per_group=n, plan=p_dn)
+                 rows_per_group=n, plan=p_dn, tile_list=tl_dn)
     out = torch.empty_like(x)
     _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
     return out
@@ -911,15 +950,30 @@ def moe_slab_plan(p: Optional[G.GemmPlan]) -> bool:
             and p.tile in G.SLAB16_TILES)
 
 
-def moe_down_combine(act, w_down, offsets, n: int, p: G.GemmPlan, topk_w, pos, out):
-    """Grouped down projection of the ``n`` permuted rows ``act`` as fp16 split-K slabs
-    (EPI "slab16"), reduced by the combine itself: out[t] = sum_j topk_w[t, j] *
-    bf16(sum_s slab_s[pos[t * k + j]]) (csrc/kernels/moe.hip moe_combine_slabs_kernel)."""
+def _moe_down_slabs(act, w_down, offsets, n: int, p: G.GemmPlan, tile_list=None):
+    """Grouped down projection of the ``n`` permuted rows ``act`` as ``p.splits`` fp16 split-K
+    slabs (EPI "slab16") in the workspace, which is returned; ``tile_list``: on the compact
+    grid (``_gemm_native``)."""
     E_local, D, F = w_down.shape
     ws = G.workspace(act.device, p.splits * max(n, 1) * D * 2)
-    _native_call("dli_gemm", _p(act), act.stride(0), _p(w_down), w_down.stride(-2), None, D,
-                 n, D, F, G.EPI["slab16"], p.tile, p.splits, None, _p(ws), _p(offsets),
-                 E_local, _st())
+    if tile_list is not None:
+        _native_call("dli_gemm_grouped_list", _p(act), act.stride(0), _p(w_down),
+                     w_down.stride(-2), None, D, n, D, F, G.EPI["slab16"], p.tile, p.splits,
+                     None, _p(ws), _p(offsets), E_local, _p(tile_list[0]), tile_list[1], _st())
+    else:
+        _native_call("dli_gemm", _p(act), act.stride(0), _p(w_down), w_down.stride(-2), None,
+                     D, n, D, F, G.EPI["slab16"], p.tile, p.splits, None, _p(ws), _p(offsets),
+                     E_local, _st())
+    return ws
+
+
+def moe_down_combine(act, w_down, offsets, n: int, p: G.GemmPlan, topk_w, pos, out,
+                     tile_list=None):
+    """Grouped down projection of the ``n`` permuted rows ``act`` as fp16 split-K slabs
+    (``_moe_down_slabs``), reduced by the combine itself: out[t] = sum_j topk_w[t, j] *
+    bf16(sum_s slab_s[pos[t * k + j]]) (csrc/kernels/moe.hip moe_combine_slabs_kernel)."""
+    D = w_down.shape[1]
+    ws = _moe_down_slabs(act, w_down, offsets, n, p, tile_list)
     T, k = topk_w.shape                  # pos: [T * k] rows (flat, as moe_align writes it)
     _native_call("dli_moe_combine_slabs", _p(out), _p(ws), p.splits, n, _p(topk_w), _p(pos),
                  T, k, D, _st())

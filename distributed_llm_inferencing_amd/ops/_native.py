@@ -80,15 +80,20 @@ _SIGS = {
     "dli_decode_attention_kv8": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, F, F, P],
     "dli_prefill_attention_paged_kv8": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I, F,
                                         F, P],
-    "dli_moe_route": [P, P, P, I, I, I, P],
+    "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],
     "dli_moe_align": [P, P, P, P, I, I, I, I, P],
+    # ..., E_local, then per tile height: list, bm, max_items (the second list nullable)
+    "dli_moe_align_tiles": [P, P, P, P, I, I, I, I, P, I, I, P, I, I, P],
     "dli_moe_gather": [P, P, P, I, I, P, P],
     "dli_moe_combine": [P, P, P, P, I, I, I, P],
     "dli_moe_combine_slabs": [P, P, I, I, P, P, I, I, I, P],
     "dli_moe_combine_add_rmsnorm": [P, P, P, I, I, P, P, I, I, I, P, F, P],
     "dli_gemm_grouped_gather": [P, I, P, I, P, I, I, I, I, I, P, P, I, P],
+    # dli_gemm's grouped call on the compact grid: ..., epi, tile, splits, arow, ws, group_off,
+    # groups, tile_list, max_items, stream
+    "dli_gemm_grouped_list": [P, I, P, I, P, I, I, I, I, I, I, I, P, P, P, I, P, I, P],
     "dli_ep_pack": [P, P, P, P, P, P, P, I, I, I, I, P],
 }
 

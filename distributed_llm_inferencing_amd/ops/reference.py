@@ -410,11 +410,14 @@ def head_candidates(h: torch.Tensor, w_slice: torch.Tensor, offset: int, c: int)
 
 
 # ----------------------------------------------------------------------------- MoE (K15, K16)
-def router_topk(router_logits: torch.Tensor, k: int):
-    """Mixtral routing: softmax -> topk -> renormalise. Returns (weights fp32 [T,k], ids int32)."""
+def router_topk(router_logits: torch.Tensor, k: int, norm_topk: bool = True):
+    """MoE routing: softmax -> topk -> renormalise (Mixtral; Qwen3-MoE with norm_topk_prob) or,
+    with ``norm_topk`` false, the softmax values as they are. Returns (weights fp32 [T,k], ids
+    int32)."""
     p = router_logits.float().softmax(-1)
     w, ids = torch.topk(p, k, dim=-1)
-    w = w / w.sum(-1, keepdim=True)
+    if norm_topk:
+        w = w / w.sum(-1, keepdim=True)
     return w, ids.to(torch.int32)
 
 

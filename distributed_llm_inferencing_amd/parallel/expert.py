@@ -61,8 +61,9 @@ class ExpertParallelMoE:
     is captured in one hipGraph per batch bucket; the only host sync per step is the
     lockstep exchange."""
 
-    def __init__(self, num_experts: int, top_k: int, group=None):
+    def __init__(self, num_experts: int, top_k: int, group=None, norm_topk: bool = True):
         self.group = group
+        self.norm_topk = norm_topk
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
         if num_experts % self.world:
@@ -199,7 +200,7 @@ class ExpertParallelMoE:
                                "token counts before the forward")
         if T > 0:
             topk_w, topk_ids = (routing if routing is not None
-                                else ops.moe_router(h, lp["router"], k))
+                                else ops.moe_router(h, lp["router"], k, self.norm_topk))
         else:
             topk_w = torch.zeros(0, k, dtype=torch.float32, device=dev)
             topk_ids = torch.zeros(0, k, dtype=torch.int32, device=dev)
@@ -282,7 +283,8 @@ class ExpertParallelEngine:
         requested = comm or os.environ.get("DLI_EP_COMM", "auto")
         self.comm = resolve_comm(requested, dev, self.ctrl_group)
         self.fallback: Optional[str] = None
-        self.moe = ExpertParallelMoE(cfg.num_experts, cfg.top_k_experts)
+        self.moe = ExpertParallelMoE(cfg.num_experts, cfg.top_k_experts,
+                                     norm_topk=cfg.norm_topk_prob)
         er = self.moe.expert_range()
         if model_dir is not None:
             params = load_ep_params(model_dir, cfg, er, dev, dtype)
