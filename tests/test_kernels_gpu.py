@@ -1,5 +1,7 @@
 """T3 kernel golden tests: every HIP kernel vs the PyTorch fp32 reference of the same op
-(ops/reference.py), on the GPU. Run on an MI355X via gpurun."""
+(ops/reference.py), on the GPU (an MI355X). Random data checks the arithmetic; an attention
+error in one key, block, head or mask bound is localised by the closed-form witnesses of
+test_kernels_attention_witness_gpu.py."""
 import math
 import os
 
