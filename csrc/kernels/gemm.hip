@@ -25,8 +25,9 @@
 //
 // Files: gemm_common.h (what the families share: block coordinates, epilogue, launcher,
 // split-K pieces), gemm_tiles.hip (the generic tiles), gemm8p.hip (8-phase ping-pong),
-// gemm4w.h + gemm4w.hip (4 waves) and gemm4wp.hip (their persistent form), gemv.hip (the
-// M <= 4 weight stream and the fused batch-1 combine). Which tile id is which kernel, tile
+// gemm4w.h + gemm4w.hip (4 waves) and gemm4wp.hip (their persistent form), gemv.h + gemv.hip
+// (the M <= 4 weight stream and the fused batch-1 combine) and gemv_fp8.hip (the same stream
+// over FP8 block-scaled weights, and their bf16 image for every other tile). Which tile id is which kernel, tile
 // size and wave layout: the one table, TILE_TABLE in ops/gemm.py; each family's dispatch
 // switch is its C++ side.
 #include "gemm_common.h"

@@ -7,7 +7,9 @@ launcher for an 8-GPU MI355X box.
     serve-master    [--port 8000]                       Flask master (dashboard + API)
     serve-worker    [--port 5000] [--gpu i]             one worker bound to one GPU (or CPU)
                     (every serve-* command takes --kv-dtype bf16|fp8: the element type of
-                    the paged KV cache, default the environment's KV_CACHE_DTYPE or bf16)
+                    the paged KV cache, default the environment's KV_CACHE_DTYPE or bf16;
+                    serve-worker / serve-node / serve-pipeline take --weight-dtype bf16|fp8:
+                    fp8 = block-scaled FP8 projection weights, default WEIGHT_DTYPE)
     serve-node      --gpus N [--base-port 5000] [--master URL]
                     one worker process per GPU (--gpu i, port base+i; every GPU stays
                     visible to every worker so a ring formed over them by join-pipeline
@@ -45,7 +47,8 @@ import sys
 import time
 
 
-def node_commands(gpus: int, base_port: int = 5000, preload: str = "", kv_dtype=None):
+def node_commands(gpus: int, base_port: int = 5000, preload: str = "", kv_dtype=None,
+                  weight_dtype=None):
     """[(argv, env)] of serve-node's workers: worker i selects GPU i of the operator's
     visibility mask with ``--gpu i`` (the mask, if any, is passed through unchanged, so
     ``HIP_VISIBLE_DEVICES=4,5,6,7 serve-node --gpus 4`` runs on physical GPUs 4-7) and sees
@@ -60,6 +63,8 @@ def node_commands(gpus: int, base_port: int = 5000, preload: str = "", kv_dtype=
                "--port", str(base_port + i), "--gpu", str(i), "--preload", preload]
         if kv_dtype:
             cmd += ["--kv-dtype", kv_dtype]
+        if weight_dtype:
+            cmd += ["--weight-dtype", weight_dtype]
         out.append((cmd, env))
     return out
 
@@ -75,9 +80,13 @@ def _serve_node(argv):
     ap.add_argument("--preload", default="")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
+                    help="fp8: block-scaled FP8 projection weights (default: WEIGHT_DTYPE, or "
+                         "the checkpoint's own)")
     a = ap.parse_args(argv)
     procs = []
-    for i, (cmd, env) in enumerate(node_commands(a.gpus, a.base_port, a.preload, a.kv_dtype)):
+    for i, (cmd, env) in enumerate(node_commands(a.gpus, a.base_port, a.preload, a.kv_dtype,
+                                                 a.weight_dtype)):
         procs.append(subprocess.Popen(cmd, env=env))
     if a.master:
         for i in range(a.gpus):
@@ -117,6 +126,9 @@ def _serve_pipeline(argv):
                     help="DP replica: serve the model as a plain node (no shard rows)")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
+                    help="fp8: block-scaled FP8 projection weights (default: WEIGHT_DTYPE, or "
+                         "the checkpoint's own)")
     a = ap.parse_args(argv)
     import torch
     from .config import get_settings
@@ -129,7 +141,8 @@ def _serve_pipeline(argv):
         torch.cuda.set_device(local)
     eng = DistributedPipelineEngine(a.model, dev, max_batch=a.max_batch,
                                     max_model_len=a.max_model_len, policy=a.policy,
-                                    shard_dir=a.shard_dir, kv_dtype=a.kv_dtype)
+                                    shard_dir=a.shard_dir, kv_dtype=a.kv_dtype,
+                                    weight_dtype=a.weight_dtype)
     eng.warmup()
     if eng.rank != 0:
         eng.serve()

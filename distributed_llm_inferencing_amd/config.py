@@ -13,6 +13,7 @@ new:
     TRANSPORT (rccl|gloo|loopback), MAX_NEW_TOKENS, KV_CACHE_FRACTION,
     MASTER_DB, MAX_BATCH, DLI_FAULT (fault-injection spec, see utils/faults.py),
     KV_CACHE_DTYPE (bf16|fp8: the paged KV cache's element type)
+    WEIGHT_DTYPE (bf16|fp8: fp8 quantises the dense llama-family projections at load)
 """
 from __future__ import annotations
 
@@ -64,6 +65,7 @@ class Settings:
     max_length: int = 100            # reference default, prompt included (views.py:351)
     kv_cache_fraction: float = 0.85
     kv_cache_dtype: str = "bf16"     # bf16 | fp8 (engine/kv_cache.py)
+    weight_dtype: str = ""           # "" (as loaded) | bf16 | fp8 (models/weights.py)
     master_db: str = str(REPO_ROOT / "db.sqlite3")
     max_batch: int = 256
     # master dispatcher threads = requests in flight to workers (each blocks on one HTTP
@@ -95,6 +97,9 @@ class Settings:
         s.kv_cache_dtype = (os.environ.get("KV_CACHE_DTYPE", "") or s.kv_cache_dtype).strip().lower()
         if s.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError(f"KV_CACHE_DTYPE={s.kv_cache_dtype!r}: expected bf16 or fp8")
+        s.weight_dtype = (os.environ.get("WEIGHT_DTYPE", "") or s.weight_dtype).strip().lower()
+        if s.weight_dtype not in ("", "bf16", "fp8"):
+            raise ValueError(f"WEIGHT_DTYPE={s.weight_dtype!r}: expected bf16 or fp8")
         s.master_db = os.environ.get("MASTER_DB", s.master_db)
         s.max_batch = _env_int("MAX_BATCH", s.max_batch)
         s.dispatch_workers = _env_int("DISPATCH_WORKERS", s.dispatch_workers)

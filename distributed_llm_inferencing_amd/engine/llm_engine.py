@@ -18,6 +18,7 @@ import torch
 
 from ..models.configs import ModelConfig, get_config
 from ..models.model import TransformerLM
+from ..models.weights import apply_weight_dtype, resolve_weight_dtype
 from ..runtime import BlockManager
 from ..tokenizer import load_tokenizer
 from .kv_cache import KVCache, auto_num_blocks, kv_element_bytes, resolve_kv_dtype
@@ -44,6 +45,10 @@ class EngineStats:
     running_sum: int = 0
     waiting_sum: int = 0
     latencies: List[float] = field(default_factory=list)
+    weight_dtype: str = "bf16"      # "fp8": FP8 block-scaled projection weights
+
+    def __call__(self) -> dict:
+        return self.snapshot()
 
     def snapshot(self) -> dict:
         lat = sorted(self.latencies[-4096:])
@@ -56,7 +61,8 @@ class EngineStats:
                 "decode_rows": self.decode_rows, "mixed_decode_rows": self.mixed_decode_rows,
                 "running_sum": self.running_sum, "waiting_sum": self.waiting_sum,
                 "tokens_per_s": (self.tokens_out / self.busy_s) if self.busy_s > 0 else 0.0,
-                "p50_latency_s": pct(0.5), "p99_latency_s": pct(0.99)}
+                "p50_latency_s": pct(0.5), "p99_latency_s": pct(0.99),
+                "weight_dtype": self.weight_dtype}
 
 
 class _HostTokens:
@@ -103,9 +109,12 @@ class LLMEngine:
                  max_prefill_tokens: int = 16384, num_layers: Optional[int] = None,
                  lm: Optional[TransformerLM] = None, lookahead: Optional[bool] = None,
                  max_kv_tokens: Optional[int] = None, mixed_steps: Optional[bool] = None,
-                 kv_dtype: Optional[str] = None, k_scale: float = 1.0, v_scale: float = 1.0):
+                 kv_dtype: Optional[str] = None, k_scale: float = 1.0, v_scale: float = 1.0,
+                 weight_dtype: Optional[str] = None):
         # "bf16" | "fp8" (None: the environment variable KV_CACHE_DTYPE, default bf16)
         self.kv_dtype = resolve_kv_dtype(kv_dtype)
+        # "bf16" | "fp8" (None: the environment variable WEIGHT_DTYPE; neither: as loaded)
+        want_w = resolve_weight_dtype(weight_dtype)
         self.cfg = get_config(model, num_layers) if isinstance(model, str) else model
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -118,6 +127,8 @@ class LLMEngine:
         else:
             self.model = TransformerLM(cfg, {k: v.to(self.device) for k, v in params.items()},
                                        device=self.device)
+        apply_weight_dtype(self.model, want_w)
+        self.weight_dtype = self.model.weight_dtype
         max_model_len = min(max_model_len, cfg.max_position)
         if num_blocks is None:
             # KV pool sized from free HBM, optionally capped
@@ -138,7 +149,7 @@ class LLMEngine:
         self.runner = StageRunner(self.model, self.kv, max_batch, self.scheduler.table_width,
                                   use_graphs=use_graphs)
         self.tokenizer = load_tokenizer(cfg, tokenizer_path)
-        self.stats = EngineStats()
+        self.stats = EngineStats(weight_dtype=self.weight_dtype)
         self.timer = StepTimer()
         self.spans = SpanLog()
         self._ids = itertools.count()
@@ -257,7 +268,7 @@ class LLMEngine:
     def memory_report(self) -> dict:
         rep = {"weights_bytes": self.model.param_bytes(), "kv_bytes": self.kv.nbytes,
                "kv_capacity_tokens": self.kv.capacity_tokens,
-               "kv_cache_dtype": self.kv.kv_dtype,
+               "kv_cache_dtype": self.kv.kv_dtype, "weight_dtype": self.weight_dtype,
                "num_blocks": self.kv.num_blocks, "free_blocks": self.bm.num_free}
         if self.device.type == "cuda":
             free, total = torch.cuda.mem_get_info(self.device)

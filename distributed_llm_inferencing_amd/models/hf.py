@@ -59,6 +59,32 @@ def find_hf_dir(root: str, name: str) -> Optional[Path]:
     return None
 
 
+def hf_weight_dtype(c: dict) -> str:
+    """``fp8`` for a checkpoint whose ``quantization_config`` is the one block this engine
+    reads — ``quant_method`` "fp8", e4m3 where a format is stated, ``weight_block_size``
+    [128, 128], ``activation_scheme`` "dynamic" or absent (activations are never quantised
+    here, so the scheme changes nothing) — ``bf16`` without the block, and an error naming
+    the field for anything else."""
+    qc = c.get("quantization_config")
+    if not qc:
+        return "bf16"
+    if qc.get("quant_method") != "fp8":
+        raise ValueError(f"quantization_config.quant_method={qc.get('quant_method')!r}: only "
+                         "'fp8' (128 x 128 block-scaled e4m3 weights) is supported")
+    fmt = qc.get("fmt", qc.get("format"))
+    if fmt is not None and "e4m3" not in str(fmt).lower():
+        raise ValueError(f"quantization_config.fmt={fmt!r}: only e4m3 is supported")
+    bs = qc.get("weight_block_size")
+    if bs is None or list(bs) != [128, 128]:
+        raise ValueError(f"quantization_config.weight_block_size={bs!r}: only [128, 128] is "
+                         "supported")
+    act = qc.get("activation_scheme")
+    if act not in (None, "dynamic"):
+        raise ValueError(f"quantization_config.activation_scheme={act!r}: only 'dynamic' "
+                         "(activations stay bf16 here) is supported")
+    return "fp8"
+
+
 def config_from_hf(c: dict, name: Optional[str] = None,
                    sliding_window: bool = False) -> ModelConfig:
     """Map a HF ``config.json`` (llama / mistral / mixtral / qwen2 / qwen3 / qwen3_moe / gpt2
@@ -71,6 +97,10 @@ def config_from_hf(c: dict, name: Optional[str] = None,
     result describes a full-attention model, so the context is capped at the window."""
     mt = c.get("model_type", "")
     name = name or c.get("_name_or_path") or mt
+    fp8 = hf_weight_dtype(c) == "fp8"
+    if fp8 and mt == "gpt2":
+        raise ValueError("quantization_config (fp8) with model_type gpt2: FP8 weights exist "
+                         "for the dense llama family only")
     if mt == "gpt2":
         d = int(c["n_embd"])
         return ModelConfig(
@@ -110,6 +140,9 @@ def config_from_hf(c: dict, name: Optional[str] = None,
             raise ValueError("qwen3_moe checkpoint without num_experts")
         inter = c["moe_intermediate_size"]
         norm_topk = bool(c.get("norm_topk_prob", False))
+    if fp8 and experts > 0:
+        raise ValueError(f"quantization_config (fp8) with num_experts={experts}: the grouped "
+                         "expert GEMMs have no FP8 form")
     d, nh = int(c["hidden_size"]), int(c["num_attention_heads"])
     rope = c.get("rope_theta")
     params = c.get("rope_parameters") or {}

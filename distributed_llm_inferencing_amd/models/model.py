@@ -54,7 +54,7 @@ class TransformerLM:
         # normed hidden state; every stage holds a vocab slice of the head
         self.vocab_parallel = False
         self.vocab_offset = 0
-        self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
+        self._bind_layers()
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -69,8 +69,33 @@ class TransformerLM:
         return cls(cfg, params, layer_start, le, device, expert_range)
 
     def _layer_params(self, i: int) -> dict:
+        """Layer ``i``'s tensors by short name; an FP8 projection and its ``_scale`` tensor
+        (models/weights.py) as one ``ops.Fp8Weight``."""
         pre = f"layers.{i}."
-        return {k[len(pre):]: v for k, v in self.params.items() if k.startswith(pre)}
+        lp = {k[len(pre):]: v for k, v in self.params.items() if k.startswith(pre)}
+        for k in [k for k in lp if k + "_scale" in lp]:
+            lp[k] = ops.Fp8Weight(lp[k], lp.pop(k + "_scale"))
+        return lp
+
+    def _bind_layers(self) -> None:
+        self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
+        fp8 = [w.numel() for lp in self.layers for w in lp.values()
+               if isinstance(w, ops.Fp8Weight)]
+        if fp8:      # the bf16 scratch of the dequantise-then-GEMM path, before the KV pool
+            ops.reserve_fp8_scratch(self.device, max(fp8))
+
+    @property
+    def weight_dtype(self) -> str:
+        """"fp8" when any projection of this stage is an FP8 block-scaled weight."""
+        return "fp8" if W.is_fp8(self.params) else "bf16"
+
+    def quantize_fp8(self) -> "TransformerLM":
+        """Quantise the four projections of every (dense llama) layer in place of their bf16
+        tensors (``weights.quantize_params``)."""
+        self.layers = []             # no second reference keeps a bf16 projection alive
+        W.quantize_params(self.cfg, self.params, inplace=True)
+        self._bind_layers()
+        return self
 
     def param_bytes(self) -> int:
         return W.nbytes(self.params)
@@ -80,7 +105,7 @@ class TransformerLM:
         self.device = torch.device(device)
         if self.cos_sin is not None:
             self.cos_sin = self.cos_sin.to(device)
-        self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
+        self._bind_layers()
         return self
 
     # ------------------------------------------------------------------ forward

@@ -6,6 +6,9 @@ llama / mixtral (per layer ``layers.{i}.``):
     attn_norm [D], wqkv [(Hq+2Hkv)*hd, D], wo [D, Hq*hd], mlp_norm [D],
     (qk_norm, Qwen3) q_norm [hd], k_norm [hd]; (qkv_bias, Qwen2) bqkv [(Hq+2Hkv)*hd]
     dense: w_gu [2F, D] (16-row gate/up interleave, see ops/reference.py), w_down [D, F]
+    FP8 weights (dense llama family only): wqkv / wo / w_gu / w_down may be float8_e4m3fn,
+    each with a fp32 ``<name>_scale`` [N/16, ceil(K/128)] beside it (ops/reference.py
+    ``dequantize_weight``); ``TransformerLM`` pairs the two into an ``ops.Fp8Weight``
     moe:   router [E, D], w_gu [E, 2F, D], w_down [E, D, F]
 gpt2 (per layer): ln1_w, ln1_b, wqkv [3D, D], bqkv [3D], wo [D, D], bo [D], ln2_w, ln2_b,
     w_fc [F, D], b_fc [F], w_proj [D, F], b_proj [D]
@@ -23,6 +26,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from .configs import ModelConfig
+from ..ops import reference as R
 from ..ops.reference import interleave_gate_up
 
 INIT_STD = 0.02
@@ -133,7 +137,145 @@ def nbytes(params: Dict[str, torch.Tensor]) -> int:
     return sum(t.numel() * t.element_size() for t in params.values())
 
 
+# ----------------------------------------------------------------------------- FP8 weights
+WEIGHT_DTYPES = ("bf16", "fp8")
+FP8_PROJECTIONS = ("wqkv", "wo", "w_gu", "w_down")
+
+
+def resolve_weight_dtype(weight_dtype: Optional[str] = None) -> Optional[str]:
+    """``"bf16"`` | ``"fp8"`` from the argument or, without one, the environment variable
+    ``WEIGHT_DTYPE``; None when neither names one (the weights stay as they come). Anything
+    else is an error."""
+    import os
+    v = os.environ.get("WEIGHT_DTYPE", "") if weight_dtype is None else weight_dtype
+    v = str(v).strip().lower()
+    if not v:
+        return None
+    if v not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype {v!r}: expected one of {WEIGHT_DTYPES}")
+    return v
+
+
+def is_fp8(params: Dict[str, torch.Tensor]) -> bool:
+    return any(t.dtype == R.FP8_W for t in params.values())
+
+
+def fp8_scratch_bytes(cfg: ModelConfig) -> int:
+    """Bytes of the bf16 scratch a model with FP8 projections reserves: its largest one."""
+    d, f = cfg.hidden_size, cfg.intermediate_size
+    return 2 * max(cfg.qkv_size * d, d * cfg.q_size, 2 * f * d, d * f)
+
+
+def check_fp8_model(cfg: ModelConfig) -> None:
+    """FP8 weights exist for the dense llama-family layers only."""
+    if cfg.arch == "gpt2":
+        raise ValueError(f"{cfg.name}: weight_dtype fp8 is not available for gpt2 (arch) models")
+    if cfg.is_moe:
+        raise ValueError(f"{cfg.name}: weight_dtype fp8 with num_experts={cfg.num_experts}: the "
+                         "grouped expert GEMMs have no FP8 form")
+
+
+def apply_weight_dtype(model, want: Optional[str]) -> None:
+    """Bring a ``TransformerLM`` to the asked weight dtype (``resolve_weight_dtype``): "fp8"
+    quantises a bf16 model's projections (refused for MoE and gpt2); an FP8 checkpoint sets
+    the dtype by itself, and an explicit "bf16" for one is an error, not a silent
+    dequantise."""
+    have = model.weight_dtype
+    if want == "fp8":
+        check_fp8_model(model.cfg)
+        if have != "fp8":
+            model.quantize_fp8()
+    elif want == "bf16" and have == "fp8":
+        raise ValueError(f"{model.cfg.name}: weight_dtype bf16 was asked for, but the loaded "
+                         "weights are FP8 (float8_e4m3fn projections with scales); they are "
+                         "not dequantised silently")
+
+
+def _u8(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.uint8) if t.dtype == R.FP8_W else t
+
+
+def _fuse(parts, names, fuse):
+    """``parts``: [(q [n, K] e4m3fn, block scales [ceil(n/128), KB])] of the unfused tensors
+    ``names``; ``fuse``: what turns their rows into the fused weight's (``torch.cat`` /
+    ``interleave_gate_up``). The scales take the same path row by row. Returns (q, scale in
+    the [N/16, KB] layout)."""
+    for (q, _), name in zip(parts, names):
+        if q.shape[0] % R.W_SCALE_ROWS:
+            raise ValueError(f"{name}: {q.shape[0]} rows, not a multiple of "
+                             f"{R.W_SCALE_ROWS}: its FP8 block scales cannot follow the rows "
+                             "into the fused weight")
+    q = fuse([_u8(q) for q, _ in parts]).contiguous().view(R.FP8_W)
+    rows = fuse([R.row_scales(s.to(q.device), pq.shape[0]) for pq, s in parts])
+    return q, R.group_scales(rows)
+
+
+def _cat(ts):
+    return torch.cat(ts, 0) if len(ts) > 1 else ts[0]
+
+
+def _interleave(ts):
+    return interleave_gate_up(ts[0], ts[1])
+
+
+def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor],
+                    inplace: bool = False) -> Dict[str, torch.Tensor]:
+    """The four projections of every dense llama layer in ``params`` as FP8 block-scaled
+    weights (``reference.quantize_weight`` of each unfused tensor: q / k / v, o, gate / up,
+    down); everything else as it is. Returns a new dict, or with ``inplace`` ``params`` itself,
+    each bf16 tensor replaced as soon as it is quantised (a caller that holds no other
+    reference then never has the bf16 and the FP8 model in memory together)."""
+    check_fp8_model(cfg)
+    out = params if inplace else dict(params)
+    hq, hkv, hd = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
+    for name in [k for k in params if k.rsplit(".", 1)[-1] in FP8_PROJECTIONS]:
+        w = params[name]
+        if w.dtype == R.FP8_W:
+            continue
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "wqkv":
+            cuts = [("q", 0, hq * hd), ("k", hq * hd, (hq + hkv) * hd),
+                    ("v", (hq + hkv) * hd, (hq + 2 * hkv) * hd)]
+            parts = [R.quantize_weight(w[a:b]) for _, a, b in cuts]
+            q, s = _fuse(parts, [f"{name}[{n}]" for n, _, _ in cuts], _cat)
+        elif leaf == "w_gu":
+            g, u = R.split_gate_up(w.t())        # rows are the interleaved axis
+            parts = [R.quantize_weight(g.t()), R.quantize_weight(u.t())]
+            q, s = _fuse(parts, [name + "[gate]", name + "[up]"], _interleave)
+        else:
+            parts = [R.quantize_weight(w)]
+            q, s = _fuse(parts, [name], _cat)
+        out[name], out[name + "_scale"] = q, s
+        del w, parts
+    return out
+
+
 # ----------------------------------------------------------------------------- HF conversion
+def _hf_proj(sd, keys, name: str, fuse, cv):
+    """One (possibly fused) projection from the HF tensors ``keys``: {name: bf16 weight}, or,
+    when the checkpoint holds ``<key>_scale_inv`` for them (an FP8 block-quantised module;
+    modules it left unconverted have none), {name: e4m3fn weight, name_scale: fp32 scales}."""
+    has = [k + "_scale_inv" in sd for k in keys]
+    if not any(has):
+        return {name: cv(fuse([sd[k] for k in keys]))}
+    if not all(has):
+        raise ValueError(f"{name}: {[k for k, h in zip(keys, has) if not h]} lack "
+                         "weight_scale_inv while the tensors fused with them have one")
+    parts = []
+    for k in keys:
+        q, s = sd[k], sd[k + "_scale_inv"]
+        if q.dtype != R.FP8_W:
+            raise ValueError(f"{k}: has a weight_scale_inv but dtype {q.dtype}, expected "
+                             "float8_e4m3fn")
+        want = (-(-q.shape[0] // R.W_BLOCK), -(-q.shape[1] // R.W_BLOCK))
+        if tuple(s.shape) != want:
+            raise ValueError(f"{k}_scale_inv: shape {tuple(s.shape)}, expected {want} "
+                             "(128 x 128 blocks)")
+        parts.append((q.detach(), s.detach().float()))
+    q, s = _fuse(parts, keys, fuse)
+    return {name: q, name + "_scale": s}
+
+
 def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
                        layers: Optional[Iterable[int]] = None, first: bool = True,
                        last: bool = True, dtype=torch.bfloat16) -> Dict[str, torch.Tensor]:
@@ -174,10 +316,9 @@ def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
         p = f"layers.{i}."
         out[p + "attn_norm"] = cv(sd[h + "input_layernorm.weight"])
         out[p + "mlp_norm"] = cv(sd[h + "post_attention_layernorm.weight"])
-        out[p + "wqkv"] = cv(torch.cat([sd[h + "self_attn.q_proj.weight"],
-                                        sd[h + "self_attn.k_proj.weight"],
-                                        sd[h + "self_attn.v_proj.weight"]], 0))
-        out[p + "wo"] = cv(sd[h + "self_attn.o_proj.weight"])
+        out.update(_hf_proj(sd, [h + f"self_attn.{n}_proj.weight" for n in "qkv"],
+                            p + "wqkv", _cat, cv))
+        out.update(_hf_proj(sd, [h + "self_attn.o_proj.weight"], p + "wo", _cat, cv))
         if cfg.qk_norm:                          # Qwen3: per-head q/k RMSNorm weights [hd]
             out[p + "q_norm"] = cv(sd[h + "self_attn.q_norm.weight"])
             out[p + "k_norm"] = cv(sd[h + "self_attn.k_norm.weight"])
@@ -212,7 +353,7 @@ def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
             out[p + "w_gu"] = cv(torch.stack(gus))
             out[p + "w_down"] = cv(torch.stack(downs))
         else:
-            out[p + "w_gu"] = cv(interleave_gate_up(sd[h + "mlp.gate_proj.weight"],
-                                                    sd[h + "mlp.up_proj.weight"]))
-            out[p + "w_down"] = cv(sd[h + "mlp.down_proj.weight"])
+            out.update(_hf_proj(sd, [h + "mlp.gate_proj.weight", h + "mlp.up_proj.weight"],
+                                p + "w_gu", _interleave, cv))
+            out.update(_hf_proj(sd, [h + "mlp.down_proj.weight"], p + "w_down", _cat, cv))
     return out

@@ -150,6 +150,123 @@ class NormedRows:
         return rmsnorm(self.residual, self.w, self.eps)
 
 
+# ----------------------------------------------------------------------------- FP8 weights
+_fp8_scratch: dict = {}
+
+
+def reserve_fp8_scratch(device, numel: int) -> None:
+    """Make the per-device bf16 scratch of ``Fp8Weight.bf16()`` hold ``numel`` elements (the
+    largest quantised projection of a model, reserved when the model is built: the KV pool
+    is sized after it and no allocation happens inside a graph capture). Not ``G.workspace``:
+    a GEMM's split-K slabs live there during the same call."""
+    device = torch.device(device)
+    if device.type != "cuda" or numel <= 0:
+        return
+    key = (device.type, device.index if device.index is not None
+           else torch.cuda.current_device())
+    buf = _fp8_scratch.get(key)
+    if buf is not None and buf.numel() >= numel:
+        return
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("the FP8 weight scratch cannot grow inside a graph capture "
+                           "(ops.reserve_fp8_scratch was not called for this weight)")
+    with G._ws_lock:                     # growth, as G.workspace
+        buf = _fp8_scratch.get(key)
+        if buf is not None and buf.numel() >= numel:
+            return
+        if buf is not None:
+            G._retired.append(buf)       # a captured graph may still write it (ops.gemm)
+        _fp8_scratch[key] = torch.empty(numel, dtype=torch.bfloat16, device=device)
+
+
+class Fp8Weight:
+    """A weight-only quantised projection: ``q`` [N, K] ``float8_e4m3fn`` and fp32 ``scale``
+    [N / 16, ceil(K / 128)], W[n, k] = float(q[n, k]) * scale[n // 16, k // 128]
+    (``reference.dequantize_weight``). Looks like its [N, K] tensor to the planner (``shape``,
+    ``dim()``, ``device``); the linear ops stream it through the FP8 GEMV kernels at
+    M <= ``G.GEMV_MAX_M`` and run every other shape on its bf16 image (``bf16()``)."""
+    __slots__ = ("q", "scale")
+    act_dtype = torch.bfloat16           # what the activations it meets are
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dtype != R.FP8_W or q.dim() != 2:
+            raise ValueError(f"Fp8Weight: q must be a 2-D float8_e4m3fn tensor, got {q.dtype} "
+                             f"{tuple(q.shape)}")
+        n, k = q.shape
+        if n % R.W_SCALE_ROWS:
+            raise ValueError(f"Fp8Weight: {n} rows, not a multiple of {R.W_SCALE_ROWS}")
+        want = (n // R.W_SCALE_ROWS, -(-k // R.W_BLOCK))
+        if scale.dtype != torch.float32 or tuple(scale.shape) != want:
+            raise ValueError(f"Fp8Weight: scale must be fp32 {want} for a weight {(n, k)}, got "
+                             f"{scale.dtype} {tuple(scale.shape)}")
+        if scale.device != q.device:
+            raise ValueError("Fp8Weight: q and scale on different devices")
+        self.q, self.scale = q.contiguous(), scale.contiguous()
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    @property
+    def dtype(self):
+        return self.q.dtype
+
+    def dim(self) -> int:
+        return 2
+
+    def numel(self) -> int:
+        return self.q.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def clone(self) -> "Fp8Weight":
+        return Fp8Weight(self.q.clone(), self.scale.clone())
+
+    def to(self, device) -> "Fp8Weight":
+        return Fp8Weight(self.q.to(device), self.scale.to(device))
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        return R.dequantize_weight(self.q, self.scale, dtype)
+
+    def bf16(self) -> torch.Tensor:
+        """The bf16 weight ``reference.dequantize_weight(q, scale, torch.bfloat16)``: on the
+        GPU a view of the per-device scratch filled by ``dli_dequant_fp8_block`` on the
+        current stream, valid until the next ``bf16()`` there (the stream orders the reuse:
+        the GEMM that reads it is enqueued before the next fill). Like ``G.workspace``, the
+        scratch assumes that one host thread at a time issues a device's ops on one stream:
+        two threads interleaving fill A, fill B, GEMM A would hand GEMM A the weight of B."""
+        if not self.q.is_cuda:
+            return self.dequantize(torch.bfloat16)
+        n, k = self.q.shape
+        reserve_fp8_scratch(self.q.device, n * k)
+        out = _fp8_scratch[(self.q.device.type, self.q.device.index)][:n * k].view(n, k)
+        _native_call("dli_dequant_fp8_block", _p(self.q), _p(self.scale), _p(out), n, k, _st())
+        return out
+
+    def gemv_ok(self, M: int, p: G.GemmPlan) -> bool:
+        """Whether the FP8 weight stream takes this call: a GEMV tile, and K and every K slice
+        in whole 16-element chunks."""
+        K = self.q.shape[1]
+        return (M <= G.GEMV_MAX_M and p.tile in G.GEMV_TILES and K % 16 == 0
+                and K % p.splits == 0 and (K // p.splits) % 16 == 0)
+
+
+def _dense(w):
+    """The tensor the bf16 kernels (or, off the GPU, the reference ops) read for ``w``."""
+    if isinstance(w, Fp8Weight):
+        return w.bf16() if w.q.is_cuda else w.dequantize(torch.float32)
+    return w
+
+
+def _inner_contig(w) -> bool:
+    return isinstance(w, Fp8Weight) or w.stride(-1) == 1
+
+
 def deferred_norm_ok(x: torch.Tensor) -> bool:
     """Whether a decode step of ``x.shape[0]`` rows runs the reduce-free GEMV chain."""
     M, K = x.shape
@@ -161,14 +278,21 @@ def _gemv_prologue(x: NormedRows, w, epi: str, plan: Optional[G.GemmPlan], C, ld
     """Run the GEMV with the deferred norm in its prologue; False if the plan has no such
     variant (the caller materialises the norm)."""
     M, K = x.shape
-    p = plan or G.plan(M, w.shape[0], K, epi)
+    p = plan or G.plan(M, w.shape[0], K, epi, G.wdt(w))
     tiles = G.GEMV_PRO_TILES.get(epi, ())
     if p.tile not in tiles or (p.tile in G.GEMV_PRO_M1_ONLY and M > 1) or M > G.GEMV_MAX_M:
         return False
     r = x.residual
     code = G.EPI["silu_mul"] if epi == "silu_mul" else 0
+    if isinstance(w, Fp8Weight) and not w.gemv_ok(M, p):
+        return False
     if ws is None and p.splits > 1:      # split K into C: slabs + the reduce kernel
         ws = G.workspace(r.device, p.splits * M * w.shape[0] * 4)
+    if isinstance(w, Fp8Weight):
+        _native_call("dli_gemv_fused_fp8", _p(r), r.stride(0), _p(x.w), x.eps, _p(w.q),
+                     _p(w.scale), w.scale.stride(0), K, _p(C), ldc, M, w.shape[0], K, code,
+                     p.tile, p.splits, _p(ws), _st())
+        return True
     _native_call("dli_gemv_fused", _p(r), r.stride(0), _p(x.w), x.eps, _p(w), w.stride(-2),
                  _p(C), ldc, M, w.shape[0], K, code, p.tile, p.splits, _p(ws), _st())
     return True
@@ -191,10 +315,16 @@ def linear_residual(x, w, residual, plan: Optional[G.GemmPlan] = None):
     decode layer as ONE kernel: full K per workgroup, the add in its epilogue (no split-K
     slabs, no reduce kernel). Other shapes take ``linear_add_rmsnorm`` without a norm."""
     M, K = x.shape
-    p = plan or G.plan(M, w.shape[0], K, "res")
+    p = plan or G.plan(M, w.shape[0], K, "res", G.wdt(w))
     if (not _use_native(x) or p.tile not in G.GEMV_RES_TILES or M > G.GEMV_MAX_M
-            or not residual.is_contiguous() or x.stride(-1) != 1 or w.stride(-1) != 1):
+            or not residual.is_contiguous() or x.stride(-1) != 1 or not _inner_contig(w)
+            or (isinstance(w, Fp8Weight) and not w.gemv_ok(M, p))):
         linear_add_rmsnorm(x, w, residual, None, 0.0)
+        return
+    if isinstance(w, Fp8Weight):
+        _native_call("dli_gemv_fused_fp8", _p(x), x.stride(0), None, 0.0, _p(w.q), _p(w.scale),
+                     w.scale.stride(0), K, _p(residual), residual.stride(0), M, w.shape[0], K,
+                     16, p.tile, 1, None, _st())
         return
     _native_call("dli_gemv_fused", _p(x), x.stride(0), None, 0.0, _p(w), w.stride(-2),
                  _p(residual), residual.stride(0), M, w.shape[0], K, 16, p.tile, 1, None, _st())
@@ -222,7 +352,7 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
     Nn = w.shape[-2]
     if plan is None:
         if group_off is None:
-            plan = G.plan(M, Nn, K, epi)
+            plan = G.plan(M, Nn, K, epi, G.wdt(w))
         else:
             plan = G.grouped_plan(M, Nn, K, epi, groups)
     out_n = Nn // 2 if epi == "silu_mul" else Nn
@@ -234,6 +364,14 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
     if splits > 1:
         ws = G.workspace(x.device, splits * M * Nn * 4)
     m_arg = M if group_off is None else rows_per_group
+    if isinstance(w, Fp8Weight):
+        if (group_off is None and w.gemv_ok(M, plan)
+                and epi in ("none", "f32", "silu_mul", "bias", "splitk")):
+            _native_call("dli_gemv_fp8", _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                         w.scale.stride(0), K, _p(out), out.stride(0), M, Nn, K, G.EPI[epi],
+                         plan.tile, splits, _p(bias), _p(ws), _st())
+            return out
+        w = w.bf16()
     if tile_list is not None:
         _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), _p(out),
                      out.stride(0), m_arg, Nn, K, G.EPI[epi], plan.tile, splits, None, _p(ws),
@@ -260,6 +398,7 @@ def linear(x, w, bias=None, epi: str = "none", out=None):
                 return y
         x = x.materialize()
     if not _use_native(x):
+        w = _dense(w)
         if epi == "silu_mul":
             y = R.silu_mul(R.linear(x, w))
         elif epi == "f32":
@@ -272,7 +411,7 @@ def linear(x, w, bias=None, epi: str = "none", out=None):
             out.copy_(y)
             return out
         return y
-    if x.stride(-1) != 1 or w.stride(-1) != 1:
+    if x.stride(-1) != 1 or not _inner_contig(w):
         raise ValueError("linear: inner dims must be contiguous")
     return _gemm_native(x, w, epi, bias=bias, out=out)
 
@@ -284,6 +423,13 @@ def _slab_gemm(x, w, p: G.GemmPlan, ws) -> int:
     M, K = x.shape
     Nn = w.shape[0]
     fmt = 1 if (G.SLAB16 and p.tile in G.SLAB16_TILES and p.splits in (2, 4, 8)) else 0
+    if isinstance(w, Fp8Weight):
+        if w.gemv_ok(M, p):              # GEMV tiles write fp32 slabs (fmt 0)
+            _native_call("dli_gemv_fp8", _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                         w.scale.stride(0), K, None, Nn, M, Nn, K, 0, p.tile, p.splits, None,
+                         _p(ws), _st())
+            return fmt
+        w = w.bf16()
     _native_call("dli_gemm", _p(x), x.stride(0), _p(w), w.stride(-2), None, Nn, M, Nn, K,
                  G.EPI["slab16"] if fmt else 0, p.tile, p.splits, None, _p(ws), None, 1, _st())
     return fmt
@@ -291,10 +437,10 @@ def _slab_gemm(x, w, p: G.GemmPlan, ws) -> int:
 
 def _splitk_plan(x, w):
     """A split-K plan for a GEMM whose partial sums feed a fused reduce, or None."""
-    if not _use_native(x) or x.stride(-1) != 1 or w.stride(-1) != 1:
+    if not _use_native(x) or x.stride(-1) != 1 or not _inner_contig(w):
         return None
     M, K = x.shape
-    p = G.plan(M, w.shape[0], K, "splitk")
+    p = G.plan(M, w.shape[0], K, "splitk", G.wdt(w))
     return p if p.splits > 1 else None
 
 

@@ -80,6 +80,11 @@ _SIGS = {
     "dli_decode_attention_kv8": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, F, F, P],
     "dli_prefill_attention_paged_kv8": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I, F,
                                         F, P],
+    # FP8 block-scaled weights: dli_gemm's GEMV case and dli_gemv_fused with the scales and
+    # their row stride after the weight pointer; the bf16 image of a weight (q, s, out, N, K)
+    "dli_gemv_fp8": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    "dli_gemv_fused_fp8": [P, I, P, F, P, P, I, I, P, I, I, I, I, I, I, I, P, P],
+    "dli_dequant_fp8_block": [P, P, P, I, I, P],
     "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

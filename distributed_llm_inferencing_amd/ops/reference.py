@@ -78,6 +78,60 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     return y.to(out_dtype or x.dtype)
 
 
+# FP8 block-scaled weights (weight-only, "W8A16"): q [N, K] OCP e4m3fn plus fp32 scales,
+#   W[n, k] = float(q[n, k]) * s[n // 16, k // 128]
+# Activations, accumulation and outputs are those of the bf16 path. The scales of every
+# quantised projection live as [N / 16, ceil(K / 128)]: 16 rows is the granularity of the
+# gate/up interleave (GU_GROUP), so a checkpoint's 128 x 128 block scales (HF
+# ``weight_scale_inv``: W = q * weight_scale_inv) survive ``cat`` and ``interleave_gate_up``
+# as long as every fused part has a multiple of 16 rows (``row_scales`` -> the weight rows'
+# permutation -> ``group_scales``).
+FP8_W = torch.float8_e4m3fn
+FP8_W_MAX = 448.0
+W_BLOCK = 128            # the checkpoint's block edge (rows and columns)
+W_SCALE_ROWS = GU_GROUP  # rows per scale group in memory
+
+
+def quantize_weight(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q [N, K] e4m3fn, block scales [ceil(N/128), ceil(K/128)] fp32) of one unfused weight:
+    per 128 x 128 block s = amax / 448 (a zero block: 1), q = fp8_rne(clamp(w / s, +-448)).
+    The clamp is part of the definition, as in ``quantize_kv``."""
+    n, k = w.shape
+    nb, kb = -(-n // W_BLOCK), -(-k // W_BLOCK)
+    wf = torch.zeros(nb * W_BLOCK, kb * W_BLOCK, dtype=torch.float32, device=w.device)
+    wf[:n, :k] = w.float()
+    blocks = wf.view(nb, W_BLOCK, kb, W_BLOCK)
+    amax = blocks.abs().amax(dim=(1, 3))
+    s = torch.where(amax > 0, amax / FP8_W_MAX, torch.ones_like(amax))
+    y = (blocks / s[:, None, :, None]).clamp(-FP8_W_MAX, FP8_W_MAX)
+    q = y.view(nb * W_BLOCK, kb * W_BLOCK)[:n, :k].contiguous().to(FP8_W)
+    return q, s
+
+
+def row_scales(block_scales: torch.Tensor, n: int) -> torch.Tensor:
+    """[ceil(N/128), KB] block scales -> one row of scales per weight row, [N, KB]."""
+    return block_scales.float().repeat_interleave(W_BLOCK, dim=0)[:n].contiguous()
+
+
+def group_scales(rows: torch.Tensor) -> torch.Tensor:
+    """[N, KB] per-row scales (constant over every 16-row group) -> the in-memory layout
+    [N / 16, KB]."""
+    if rows.shape[0] % W_SCALE_ROWS:
+        raise ValueError(f"{rows.shape[0]} weight rows: FP8 scales need a multiple of 16")
+    return rows[::W_SCALE_ROWS].contiguous()
+
+
+def dequantize_weight(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """The reconstructed weight: the fp32 product float(q) * s[n // 16, k // 128], rounded
+    once to ``dtype``."""
+    n, k = q.shape
+    if s.shape != (n // W_SCALE_ROWS, -(-k // W_BLOCK)) or n % W_SCALE_ROWS:
+        raise ValueError(f"scales {tuple(s.shape)} do not fit an FP8 weight {(n, k)}: expected "
+                         f"[N / 16, ceil(K / 128)]")
+    se = s.float().repeat_interleave(W_SCALE_ROWS, dim=0).repeat_interleave(W_BLOCK, dim=1)
+    return (q.float() * se[:, :k]).to(dtype)
+
+
 def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     """[F, K] x2 -> [2F, K] in the 16-row interleaved layout (see module doc)."""
     f, k = gate.shape

@@ -109,7 +109,7 @@ class StageWorker:
                  block_size: int, max_batch: int, table_width: int, seed: int = 0,
                  use_graphs: Optional[bool] = None, params=None, dtype=torch.bfloat16,
                  vocab_slice: Optional[Tuple[int, int]] = None, max_tokens: int = 0,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
         self.cfg, self.plan = cfg, plan
         self.device = torch.device(device)
         self.max_batch = max_batch
@@ -120,6 +120,8 @@ class StageWorker:
         else:
             self.model = TransformerLM(cfg, {k: v.to(self.device) for k, v in params.items()},
                                        plan.start_layer, plan.end_layer, self.device)
+        # "bf16" | "fp8" (None: the environment variable WEIGHT_DTYPE; neither: as loaded)
+        W.apply_weight_dtype(self.model, W.resolve_weight_dtype(weight_dtype))
         self.vocab_parallel = vocab_slice is not None
         if self.vocab_parallel:
             lo, hi = vocab_slice
@@ -226,17 +228,21 @@ H_VP = 13          # ctrl header word: 1 = vocab-parallel head for this step
 
 def _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction, cap_tokens,
                            vocab_slice: Optional[Tuple[int, int]] = None,
-                           loaded: bool = False, kv_dtype: Optional[str] = None):
+                           loaded: bool = False, kv_dtype: Optional[str] = None,
+                           fp8_weights: bool = False):
     """KV blocks of this stage's pool, sized before its weights are loaded: the stage's own
     parameter bytes (plus its vocab-parallel head slice) are still to come, and with every
     rank on one device (``DLI_SAME_DEVICE=1``) so are every other rank's — summed over the
     ranks, or 8 ranks each sizing against the empty device over-commit it (Llama-3-70B pp8 on
-    one GPU ran out of memory: profiles/r6/README.md)."""
-    pending = 0
+    one GPU ran out of memory: profiles/r6/README.md). ``fp8_weights``: the stage will hold
+    FP8 projections, whose bf16 scratch (``ops.reserve_fp8_scratch``) is allocated when the
+    model is built, after this; a model quantised at start-up is counted at its bf16 bytes,
+    its peak."""
+    pending = W.fp8_scratch_bytes(cfg) if fp8_weights else 0
     if not loaded:                      # the shard-file path loads before sizing the pool
         shapes = W.stage_param_shapes(cfg, plan.start_layer, plan.end_layer, plan.first,
                                       plan.last)
-        pending = sum(int(np.prod(s)) for s in shapes.values()) * 2
+        pending += sum(int(np.prod(s)) for s in shapes.values()) * 2
         if vocab_slice is not None:
             pending += (vocab_slice[1] - vocab_slice[0]) * cfg.hidden_size * 2
     if os.environ.get("DLI_SAME_DEVICE", "0") == "1" and dist.is_initialized():
@@ -324,7 +330,7 @@ class PipelineHead:
         self.vp = stage.vocab_parallel
         self.M = microbatches or num_microbatches(self.N, self.vp)
         assert self.N == 1 or self.M >= self.N + (3 if self.vp else 1), "too few microbatches"
-        self.stats = EngineStats()
+        self.stats = EngineStats(weight_dtype=stage.model.weight_dtype)
         self.host_s = 0.0          # head host time in ticks, excluding transport waits
         self.ticks = 0
         self.tick_log = [] if os.environ.get("DLI_PP_TICK_LOG", "0") == "1" else None
@@ -758,7 +764,8 @@ def build_stage(cfg: ModelConfig, rank: int, world: int, device, max_batch: int,
                 num_blocks: Optional[int] = None, dtype=torch.bfloat16,
                 vocab_parallel: bool = False, microbatches: Optional[int] = None,
                 max_tokens: int = 0, shard_dir: Optional[str] = None,
-                max_kv_tokens: int = 0, kv_dtype: Optional[str] = None):
+                max_kv_tokens: int = 0, kv_dtype: Optional[str] = None,
+                weight_dtype: Optional[str] = None):
     if shard_dir is not None:
         from ..shard.writer import stage_plan_from_metadata
         plans = [stage_plan_from_metadata(read_shard_dir(shard_dir, i, world)[1])
@@ -776,14 +783,17 @@ def build_stage(cfg: ModelConfig, rank: int, world: int, device, max_batch: int,
         # the same block ids (the head's allocator), so all take the smallest pool
         cap = _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction,
                                      cap_tokens=max_kv_tokens, vocab_slice=vs,
-                                     loaded=params is not None, kv_dtype=kv_dtype)
+                                     loaded=params is not None, kv_dtype=kv_dtype,
+                                     fp8_weights=(W.resolve_weight_dtype(weight_dtype) == "fp8"
+                                                  or (params is not None and W.is_fp8(params))))
         t = torch.tensor([cap], dtype=torch.int64,
                          device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)     # block ids are global: same pool size
         num_blocks = int(t.item())
     stage = StageWorker(cfg, plan, device, num_blocks, block_size, max_batch, table_width,
                         seed=seed, use_graphs=use_graphs, dtype=dtype, vocab_slice=vs,
-                        max_tokens=max_tokens, params=params, kv_dtype=kv_dtype)
+                        max_tokens=max_tokens, params=params, kv_dtype=kv_dtype,
+                        weight_dtype=weight_dtype)
     return stage, plans, num_blocks, table_width
 
 
@@ -797,8 +807,9 @@ class DistributedPipelineEngine:
                  use_graphs=None, max_prefill_tokens: int = 16384, num_blocks=None,
                  dtype=torch.bfloat16, vocab_parallel: Optional[bool] = None,
                  shard_dir: Optional[str] = None, max_kv_tokens: int = 0,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
         self.kv_dtype = resolve_kv_dtype(kv_dtype)
+        weight_dtype = W.resolve_weight_dtype(weight_dtype)     # an unknown value stops here
         self.rank, self.world = init_distributed(device=torch.device(device)
                                                  if torch.device(device).type == "cuda" else None)
         if shard_dir is not None:
@@ -822,7 +833,7 @@ class DistributedPipelineEngine:
             policy=policy, seed=seed, use_graphs=use_graphs, num_blocks=num_blocks, dtype=dtype,
             vocab_parallel=self.vocab_parallel, microbatches=self.microbatches,
             max_tokens=max_tokens, shard_dir=shard_dir, max_kv_tokens=max_kv_tokens,
-            kv_dtype=self.kv_dtype)
+            kv_dtype=self.kv_dtype, weight_dtype=weight_dtype)
         esz = torch.empty(0, dtype=dtype).element_size()
         D = self.cfg.hidden_size
         # mailbox sizes of the IPC data plane: a whole step's hidden rows on r -> r + 1; the
@@ -893,7 +904,7 @@ class LocalPipeline:
                  policy: str = "even", seed: int = 0, use_graphs=None, params=None,
                  dtype=torch.bfloat16, plans: Optional[List[StagePlan]] = None,
                  stage_params: Optional[List[Dict[str, torch.Tensor]]] = None, tokenizer=None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
         self.cfg = get_config(model) if isinstance(model, str) else model
         self.kv_dtype = resolve_kv_dtype(kv_dtype)
         self.N = num_stages
@@ -908,13 +919,14 @@ class LocalPipeline:
                 sp = {k: v for k, v in params.items() if _param_in_stage(k, p, self.cfg)}
             self.stages.append(StageWorker(self.cfg, p, device, num_blocks, block_size,
                                            max_batch, tw, seed, use_graphs, params=sp,
-                                           dtype=dtype, kv_dtype=self.kv_dtype))
+                                           dtype=dtype, kv_dtype=self.kv_dtype,
+                                           weight_dtype=weight_dtype))
         self.sched = Scheduler(BlockManager(num_blocks, block_size), max_seqs_per_mb=max_batch,
                                num_microbatches=num_stages, eos_token_id=self.cfg.eos_token_id,
                                max_model_len=max_model_len, table_width=tw,
                                native_decode=os.environ.get("DLI_NATIVE_SCHED", "1") == "1")
         self.tok = tokenizer or load_tokenizer(self.cfg)
-        self.stats = EngineStats()
+        self.stats = EngineStats(weight_dtype=self.stages[0].model.weight_dtype)
         self._ids = 0
         self._k = 0
         self._inflight: Dict[int, tuple] = {}

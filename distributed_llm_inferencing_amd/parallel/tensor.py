@@ -33,6 +33,9 @@ from ..ops.reference import GU_GROUP
 
 def shard_param(name: str, t: torch.Tensor, cfg, rank: int, world: int) -> torch.Tensor:
     hd, hq, hkv = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+    if t.dtype == torch.float8_e4m3fn or name.endswith("_scale"):
+        raise ValueError(f"{name}: tensor parallel mode slices weights and cannot slice an FP8 "
+                         "block-scaled one (its scales cover 128-column blocks)")
     if name.endswith(".wqkv"):
         q = t[: hq * hd].view(hq, hd, -1)
         k = t[hq * hd:(hq + hkv) * hd].view(hkv, hd, -1)
@@ -77,7 +80,10 @@ class TPReduce:
 class TensorParallelEngine:
     def __init__(self, model: str, device, max_batch: int = 256, max_model_len: int = 2048,
                  seed: int = 0, num_blocks: Optional[int] = None, dtype=torch.bfloat16,
-                 max_prefill_tokens: int = 16384):
+                 max_prefill_tokens: int = 16384, weight_dtype: Optional[str] = None):
+        if W.resolve_weight_dtype(weight_dtype) == "fp8":
+            raise ValueError("tensor parallel mode has no FP8 weights (weight_dtype fp8): it "
+                             "slices the projections across ranks")
         from .transport import init_distributed
         dev = torch.device(device)
         self.rank, self.world = init_distributed(device=dev if dev.type == "cuda" else None)

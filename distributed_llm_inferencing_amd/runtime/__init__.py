@@ -316,7 +316,8 @@ class DecodeCore:
 
 
 _DT = {"BF16": torch.bfloat16, "F16": torch.float16, "F32": torch.float32, "I32": torch.int32,
-       "I64": torch.int64, "U8": torch.uint8, "I8": torch.int8}
+       "I64": torch.int64, "U8": torch.uint8, "I8": torch.int8,
+       "F8_E4M3": torch.float8_e4m3fn}
 
 
 class SafetensorsFile:

@@ -43,9 +43,13 @@ def export_shards(model_name: str, num_shards: int, output_dir: str = "model_sha
     the HF model, shard_model.py:37): each stage reads only its own tensors from it."""
     from safetensors.torch import save_file
     if hf_dir is not None:
-        from ..models.hf import config_from_hf
-        cfg = config_from_hf(json.loads((Path(hf_dir) / "config.json").read_text()),
-                             model_name, sliding_window=True)
+        from ..models.hf import config_from_hf, hf_weight_dtype
+        hf_cfg = json.loads((Path(hf_dir) / "config.json").read_text())
+        cfg = config_from_hf(hf_cfg, model_name, sliding_window=True)
+        if hf_weight_dtype(hf_cfg) == "fp8":
+            raise ValueError(f"{hf_dir}: an FP8 checkpoint (quantization_config) cannot be "
+                             "sharded: the shard writer exports bf16 / fp16 / fp32 stages only. "
+                             "Serve it whole from the model cache")
     cfg = cfg or get_config(model_name)
     plans = plan_stages(cfg, num_shards, policy)
     root = model_dir(output_dir, model_name)

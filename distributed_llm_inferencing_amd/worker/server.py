@@ -83,6 +83,11 @@ class WorkerState:
         from ..engine.kv_cache import resolve_kv_dtype
         self.engine_kwargs["kv_dtype"] = resolve_kv_dtype(
             self.engine_kwargs.get("kv_dtype") or getattr(settings, "kv_cache_dtype", None))
+        # likewise the weight dtype (bf16 | fp8; None: a checkpoint's own)
+        from ..models.weights import resolve_weight_dtype
+        self.engine_kwargs["weight_dtype"] = resolve_weight_dtype(
+            self.engine_kwargs.get("weight_dtype") or getattr(settings, "weight_dtype", "")
+            or None)
         if gpu and self.engine_kwargs.get("num_blocks") is None:
             # a worker may serve several models (/load_model per name): each engine's KV
             # pool is capped at max_batch x max_model_len tokens (DLI_KV_MAX_TOKENS
@@ -231,7 +236,8 @@ class WorkerState:
                                             num_blocks=kw["num_blocks"], shard_dir=shard_dir,
                                             dtype=_shard_dtype(shard_dir, rank),
                                             max_kv_tokens=kw.get("max_kv_tokens") or 0,
-                                            kv_dtype=kw.get("kv_dtype"))
+                                            kv_dtype=kw.get("kv_dtype"),
+                                            weight_dtype=kw.get("weight_dtype"))
             eng.warmup()
             self._pipe_engine = eng
             ch = eng.channel
@@ -404,7 +410,8 @@ class WorkerState:
                                  max_model_len=kw["max_model_len"],
                                  num_blocks=kw["num_blocks"] or 4096, params=params,
                                  plans=plans, tokenizer=self.tokenizers.get(name),
-                                 kv_dtype=kw.get("kv_dtype"))
+                                 kv_dtype=kw.get("kv_dtype"),
+                                 weight_dtype=kw.get("weight_dtype"))
             svc = EngineService(pipe, name=f"{name.replace('/', '_')}-shards")
             self.shard_pipes[key] = svc
             return svc
@@ -439,6 +446,8 @@ def _shard_dtype(shard_dir: str, rank: int) -> torch.dtype:
     with safe_open(f, "pt") as h:
         keys = list(h.keys())
         code = h.get_slice(keys[0]).get_dtype() if keys else "BF16"   # header only
+    if code == "F8_E4M3":      # FP8 weights are weight-only: the activations are bf16
+        return torch.bfloat16
     return {"F32": torch.float32, "F16": torch.float16}.get(code, torch.bfloat16)
 
 
@@ -665,6 +674,9 @@ def main(argv=None):
     ap.add_argument("--max-batch", type=int, default=None)
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
+                    help="fp8: quantise the dense llama-family projections to block-scaled FP8 "
+                         "(default: WEIGHT_DTYPE, or the checkpoint's own)")
     ap.add_argument("--server", default="werkzeug", choices=["werkzeug", "uvicorn", "aiohttp"],
                     help="uvicorn: ASGI front (worker/asgi.py: /inference as a coroutine per "
                          "request) over the same Flask app; aiohttp: the same ASGI front on "
@@ -684,6 +696,9 @@ def main(argv=None):
     if a.kv_dtype:
         s.kv_cache_dtype = a.kv_dtype
         kw = dict(kw or {}, kv_dtype=a.kv_dtype)
+    if a.weight_dtype:
+        s.weight_dtype = a.weight_dtype
+        kw = dict(kw or {}, weight_dtype=a.weight_dtype)
     app = create_worker_app(s, dev, kw)
     for m in [m for m in a.preload.split(",") if m]:
         app.extensions["dli_worker"].load_model(m)
