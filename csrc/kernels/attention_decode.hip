@@ -14,7 +14,7 @@
 //                                                in the prefill kernel)
 // With >1 split the per-split (m, l, O) go to a workspace merged by a second kernel.
 // decode_attn_fused_kernel (the decode-graph default) runs the same tile loop after a
-// prologue that does the work of dli_splitk_rope_cache[_x] (qkv_rope.h) inside the attention
+// prologue that does the work of dli_splitk_rope_cache (qkv_rope.h) inside the attention
 // wave: the QKV GEMM's split-K slabs (or its bf16 rows) are reduced, biased and normalised
 // where the model asks for it, q/k rotated and k/v written to the paged cache.
 // Forms: decode_attn_kernel (a wave per item, one tile per round), decode_attn_wg_kernel (a
@@ -27,91 +27,6 @@
 // [nblk,Hkv,bs,hd] (token-major: the per-step cache write is a contiguous row),
 // block_tables [B, max_blocks], out [B, Hq, hd].
 #include "attention_decode.h"
-
-// The tile loop of the one-tile-per-round kernels: one wave = one (sequence, kv head, split)
-// item with its Q^T fragments already in registers. Over tokens [s_begin, s_end) it leaves
-// the unnormalised O rows in o_acc, the running max of head `col` in m_run and this lane's
-// partial denominator in l_part.
-template <int HD>
-__device__ __forceinline__ void decode_attn_loop(
-    const bf16x8 (&qf)[HD / 32], u16* vt, int lane, int b, int kvh, int s_begin, int s_end,
-    const u16* __restrict__ k_cache, const u16* __restrict__ v_cache,
-    const int* __restrict__ block_tables, int max_blocks, int hkv, int block_size,
-    float scale_log2, int bt_lane0, f32x4 (&o_acc)[HD / 16], float& m_run, float& l_part) {
-  constexpr int DB = HD / 16;     // 16-wide output column blocks (= V pieces per lane)
-  constexpr int KK = HD / 32;
-  constexpr int VROW = HD + 16;   // padded LDS row of the V tile, in u16
-  constexpr int VCH = HD / 8;     // 16-B chunks per V row
-  const int col = lane & 15, grp = lane >> 4;
-  const int* bt = block_tables + (long)b * max_blocks;
-  // the split's block ids, one per lane, read once per 64-block window (token -> block by a
-  // lane shuffle): the per-tile K/V loads no longer wait on a dependent block-table load
-  const int last_blk = max(s_end - 1, 0) / block_size;
-  int win = s_begin / block_size;
-  int bt_lane = bt_lane0;
-  const long kv_head_stride = (long)block_size * HD;           // elements per (blk, head)
-  m_run = -INFINITY;                // running max for head `col` (replicated over groups)
-  l_part = 0.f;                     // this lane's partial denominator for head `col`
-#pragma unroll
-  for (int i = 0; i < DB; ++i) o_acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  for (int t0 = s_begin; t0 < s_end; t0 += DEC_TILE) {
-    if ((min(t0 + DEC_TILE, s_end) - 1) / block_size - win >= 64) {   // wave-uniform
-      win = t0 / block_size;
-      bt_lane = bt[min(win + lane, last_blk)];
-    }
-    // ---- issue every global load of the tile up front (K fragments AND V fragments)
-    uint4 kreg[2][KK];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      int tok = t0 + 16 * s + col;
-      tok = tok < s_end ? tok : s_end - 1;                     // clamp: always-written rows
-      const int blk = __shfl(bt_lane, tok / block_size - win, 64), off = tok % block_size;
-      const u16* kp = k_cache + ((long)blk * hkv + kvh) * kv_head_stride + (long)off * HD;
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk)
-        kreg[s][kk] = *reinterpret_cast<const uint4*>(kp + kk * 32 + grp * 8);
-    }
-    // V rows t0 .. t0+31 (row-major, 16-B chunks; piece lane + 64m = row r, chunk c)
-    uint4 vreg[DB];
-#pragma unroll
-    for (int m = 0; m < DB; ++m) {
-      const int piece = lane + 64 * m, r = piece / VCH, c = piece % VCH;
-      const int tok = min(t0 + r, s_end - 1);                  // clamp: always-written rows
-      const int blk = __shfl(bt_lane, tok / block_size - win, 64), off = tok % block_size;
-      vreg[m] = *reinterpret_cast<const uint4*>(
-          v_cache + ((long)blk * hkv + kvh) * kv_head_stride + (long)off * HD + c * 8);
-    }
-    f32x4 s_acc[2];
-    decode_scores<HD>(kreg, qf, s_acc);
-    float p[8];
-    decode_softmax_update<HD, false>(s_acc, t0, s_end, grp, scale_log2, m_run, l_part, o_acc, p);
-    // stage the V tile in this wave's LDS rows (previous tile's reads retired below)
-#pragma unroll
-    for (int m = 0; m < DB; ++m) {
-      const int piece = lane + 64 * m, r = piece / VCH, c = piece % VCH;
-      *reinterpret_cast<uint4*>(vt + r * VROW + c * 8) = vreg[m];
-    }
-    const bf16x8 pa = decode_pack_p(p);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // V tile writes landed (same wave)
-    // B operand: rows (tokens) 4grp+q and 16+4grp+q, columns 16i + 4p, transposed by
-    // ds_read_b64_tr_b16 (lane 4q+p of each 16-lane group names row q, columns 4p..4p+3)
-    const int qrow = (lane >> 2) & 3, pcol = lane & 3;
-#pragma unroll
-    for (int i = 0; i < DB; ++i) {
-      const u16* a0 = vt + (4 * grp + qrow) * VROW + 16 * i + 4 * pcol;
-      const u16* a1 = vt + (16 + 4 * grp + qrow) * VROW + 16 * i + 4 * pcol;
-      s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4*)(a0));
-      s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4*)(a1));
-      s16x8 w = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      o_acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, *reinterpret_cast<bf16x8*>(&w),
-                                                        o_acc[i], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before next overwrite
-  }
-}
 
 template <int HD>
 __device__ __forceinline__ void decode_attn_core(
@@ -298,10 +213,10 @@ __global__ void __launch_bounds__(256) decode_attn_wg_kernel(
 // wave w takes the w-th quarter of the context's tiles, and the four partial (m, l, O) merge
 // through LDS (the V-tile rows are reused for the O partials).
 //
-// X (dli_decode_attention_fused_x, the Qwen families): a QKV bias [N] (or null) is added to
+// X (the Qwen families): a QKV bias [N] (or null) is added to
 // the fp32 slab sum before its rounding to bf16 (Qwen2); then every q head and the k row are
 // RMS-normalised over their 128 dims with q_norm_w / k_norm_w (or null) and rounded to bf16
-// before the rotation (Qwen3). The rounding points are those of dli_splitk_rope_cache_x. A
+// before the rotation (Qwen3). The rounding points are those of dli_splitk_rope_cache. A
 // query head's 128 dims sit in the 4 lanes col + 16 grp, so its sum of squares is the xor-16
 // and xor-32 shuffles; the bf16 q values wait in the fragment registers themselves between
 // the two passes (no extra VGPRs live across the reduction; without norm weights the second
@@ -767,9 +682,6 @@ extern "C" int dli_decode_set_pipe(int v) {
   return old;
 }
 
-// the mode the next dli_decode_attention call applies
-extern "C" int dli_decode_get_pipe() { return g_decode_pipe; }
-
 // a workgroup per (sequence, kv head) item while the items alone would leave most CUs idle
 // (<= 256 items: B <= 32 at 8 kv heads), else a wave per item; tests force either form with
 // dli_decode_set_form(1 = wave per item, DEC_WAVES = workgroup per item, 0 = automatic)
@@ -783,42 +695,48 @@ static bool wg_form(long items) {
   return g_decode_form == DEC_WAVES || (g_decode_form != 1 && items <= 256);
 }
 
-// window > 0: sliding-window attention (decode_win_lo); the splits divide the longest span a
-// sequence can have, min(max_context, window) tokens, each offset by its sequence's start,
-// so the work follows the window and no split is empty for every sequence
-extern "C" int dli_decode_attention_win(void* out, const void* q, int q_stride,
-                                        const void* k_cache, const void* v_cache,
-                                        const int* block_tables, int max_blocks,
-                                        const int* context_lens, int B, int hq, int hkv, int hd,
-                                        int block_size, float scale, int max_context,
-                                        int num_splits, void* workspace, int window,
-                                        hipStream_t st) {
+// 2 = automatic: the pipelined kernel for splits of >= 768 tokens (measured: +18 % at ctx
+// 1000, B 64; within 3 % slower at ctx 33-100, B 512, where the per-item dependent loads
+// (context length -> block table -> K/V) rather than tile rounds bound the time)
+static bool decode_uses_pipe(int hd, int split_tokens) {
+  return hd == 128 && (g_decode_pipe == 1 || (g_decode_pipe == 2 && split_tokens >= 768));
+}
+
+// whether dli_decode_attention would take the pipelined kernel for a bf16 cache, a span of
+// min(max_context, window) keys and num_splits KV splits (the fused kernel has no such form)
+extern "C" int dli_decode_uses_pipe(int hd, int span, int num_splits) {
+  return decode_uses_pipe(hd, decode_split_tokens(span, num_splits < 1 ? 1 : num_splits));
+}
+
+// window: see DecodeSplits. kv_fp8: the caches hold e4m3fn bytes with the scales k_scale,
+// v_scale (> 0; the wave-per-item kernel of attention_decode_fp8.hip); else bf16, scales 1.
+extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, const void* k_cache,
+                                    const void* v_cache, const int* block_tables, int max_blocks,
+                                    const int* context_lens, int B, int hq, int hkv, int hd,
+                                    int block_size, float scale, int max_context, int num_splits,
+                                    void* workspace, int window, int kv_fp8, float k_scale,
+                                    float v_scale, hipStream_t st) {
   if (B <= 0) return 0;
-  if (window < 0) window = 0;
-  if (window > 0 && window < max_context) max_context = window;
-  if (hq % hkv || hq / hkv > 16 || block_size % 16 || (hd != 64 && hd != 128))
+  DecodeSplits g;
+  if (!kv_scales_ok(kv_fp8, k_scale, v_scale) ||
+      !decode_splits(B, hq, hkv, hd, block_size, max_context, num_splits, workspace, window, g))
     return (int)hipErrorInvalidValue;
-  if (num_splits < 1) num_splits = 1;
-  if (num_splits > 1 && workspace == nullptr) return (int)hipErrorInvalidValue;
-  int split_tokens = (max_context + num_splits - 1) / num_splits;
-  split_tokens = ((split_tokens + DEC_TILE - 1) / DEC_TILE) * DEC_TILE;
-  if (split_tokens <= 0) split_tokens = DEC_TILE;
-  float* ws_o = (float*)workspace;
-  float* ws_ml = ws_o ? ws_o + (long)B * hq * num_splits * hd : nullptr;
+  if (kv_fp8)
+    return decode_attention_fp8_launch(out, q, q_stride, k_cache, v_cache, block_tables,
+                                       max_blocks, context_lens, B, hq, hkv, hd, block_size,
+                                       scale, g, k_scale, v_scale, st);
+  num_splits = g.num_splits;
+  window = g.window;
   const float scale_log2 = scale * 1.4426950408889634f;
   const long items = (long)B * hkv * num_splits;
-  // 2 = automatic: the pipelined kernel for splits of >= 768 tokens (measured: +18 % at ctx
-  // 1000, B 64; within 3 % slower at ctx 33-100, B 512, where the per-item dependent loads
-  // (context length -> block table -> K/V) rather than tile rounds bound the time)
-  const bool use_pipe = g_decode_pipe == 1 || (g_decode_pipe == 2 && split_tokens >= 768);
-  if (hd == 128 && use_pipe) {
+  if (decode_uses_pipe(hd, g.split_tokens)) {
     // 8 waves per CU x 256 CUs; each wave walks items gw, gw + nw, ...
     const long wgs = (items + DEC_WAVES - 1) / DEC_WAVES;
     dim3 gp((int)(wgs < 512 ? wgs : 512));
     decode_attn_pipe_kernel<128><<<gp, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
         block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2, num_splits,
-        split_tokens, ws_o, ws_ml, window);
+        g.split_tokens, g.ws_o, g.ws_ml, window);
   } else if (hd == 128 && num_splits == 1 && wg_form(items)) {
     decode_attn_wg_kernel<<<(int)items, 64 * DEC_WAVES, 0, st>>>(
         (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
@@ -829,25 +747,16 @@ extern "C" int dli_decode_attention_win(void* out, const void* q, int q_stride,
       decode_attn_kernel<128, 4><<<grid, 64 * DEC_WAVES, 0, st>>>(
           (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
           block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2,
-          num_splits, split_tokens, ws_o, ws_ml, window);
+          num_splits, g.split_tokens, g.ws_o, g.ws_ml, window);
     else
       decode_attn_kernel<64, 1><<<grid, 64 * DEC_WAVES, 0, st>>>(
           (u16*)out, (const u16*)q, q_stride, (const u16*)k_cache, (const u16*)v_cache,
           block_tables, max_blocks, context_lens, B, hq, hkv, block_size, scale_log2,
-          num_splits, split_tokens, ws_o, ws_ml, window);
+          num_splits, g.split_tokens, g.ws_o, g.ws_ml, window);
   }
-  if (num_splits > 1) return decode_reduce_launch(out, ws_o, ws_ml, B, hq, hd, num_splits, st);
+  if (num_splits > 1)
+    return decode_reduce_launch(out, g.ws_o, g.ws_ml, B, hq, hd, num_splits, st);
   DLI_RETURN_LAUNCH();
-}
-
-extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, const void* k_cache,
-                                    const void* v_cache, const int* block_tables, int max_blocks,
-                                    const int* context_lens, int B, int hq, int hkv, int hd,
-                                    int block_size, float scale, int max_context, int num_splits,
-                                    void* workspace, hipStream_t st) {
-  return dli_decode_attention_win(out, q, q_stride, k_cache, v_cache, block_tables, max_blocks,
-                                  context_lens, B, hq, hkv, hd, block_size, scale, max_context,
-                                  num_splits, workspace, 0, st);
 }
 
 // Fused split-K QKV reduce + RoPE + KV-cache write + decode attention (one KV split, head
@@ -855,17 +764,15 @@ extern "C" int dli_decode_attention(void* out, const void* q, int q_stride, cons
 // with splits == 0 the bf16 QKV rows [B, (hq + 2 hkv) * 128] of an unsplit GEMM.
 // fmt: 0 = fp32 slabs (or the bf16 rows when splits == 0), 1 = fp16 x 1/16 slabs (EPI_SLAB16)
 // window > 0: sliding-window attention (decode_win_lo)
-// bias [N] / q_norm_w, k_norm_w [128]: see qkv_extras_ok; all null =
-// dli_decode_attention_fused_win
-extern "C" int dli_decode_attention_fused_x(void* out, const void* ws, int splits,
-                                            const int* positions, const int* slot_mapping,
-                                            const float* cos_sin, void* k_cache, void* v_cache,
-                                            const int* block_tables, int max_blocks,
-                                            const int* context_lens, int B, int hq, int hkv,
-                                            int hd, int block_size, float scale, int fmt,
-                                            int window, const void* bias, const void* q_norm_w,
-                                            const void* k_norm_w, float qk_eps,
-                                            hipStream_t st) {
+// bias [N] / q_norm_w, k_norm_w [128]: see qkv_extras_ok; all null = the plain prologue
+extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
+                                          const int* positions, const int* slot_mapping,
+                                          const float* cos_sin, void* k_cache, void* v_cache,
+                                          const int* block_tables, int max_blocks,
+                                          const int* context_lens, int B, int hq, int hkv,
+                                          int hd, int block_size, float scale, int fmt,
+                                          int window, const void* bias, const void* q_norm_w,
+                                          const void* k_norm_w, float qk_eps, hipStream_t st) {
   if (B <= 0) return 0;
   if (window < 0) window = 0;
   if (hd != 128 || hq % hkv || hq / hkv > 16 || block_size % 16 ||
@@ -907,33 +814,6 @@ extern "C" int dli_decode_attention_fused_x(void* out, const void* ws, int split
 #undef DLI_DAF
 #undef DLI_DAFX
   DLI_RETURN_LAUNCH();
-}
-
-extern "C" int dli_decode_attention_fused_win(void* out, const void* ws, int splits,
-                                              const int* positions, const int* slot_mapping,
-                                              const float* cos_sin, void* k_cache,
-                                              void* v_cache, const int* block_tables,
-                                              int max_blocks, const int* context_lens, int B,
-                                              int hq, int hkv, int hd, int block_size,
-                                              float scale, int fmt, int window,
-                                              hipStream_t st) {
-  return dli_decode_attention_fused_x(out, ws, splits, positions, slot_mapping, cos_sin,
-                                      k_cache, v_cache, block_tables, max_blocks, context_lens,
-                                      B, hq, hkv, hd, block_size, scale, fmt, window, nullptr,
-                                      nullptr, nullptr, 0.f, st);
-}
-
-extern "C" int dli_decode_attention_fused(void* out, const void* ws, int splits,
-                                          const int* positions, const int* slot_mapping,
-                                          const float* cos_sin, void* k_cache, void* v_cache,
-                                          const int* block_tables, int max_blocks,
-                                          const int* context_lens, int B, int hq, int hkv,
-                                          int hd, int block_size, float scale, int fmt,
-                                          hipStream_t st) {
-  return dli_decode_attention_fused_win(out, ws, splits, positions, slot_mapping, cos_sin,
-                                        k_cache, v_cache, block_tables, max_blocks,
-                                        context_lens, B, hq, hkv, hd, block_size, scale, fmt, 0,
-                                        st);
 }
 
 extern "C" long dli_decode_attention_workspace_bytes(int B, int hq, int hd, int num_splits) {

@@ -515,22 +515,29 @@ __global__ void __launch_bounds__(512) prefill_attn32_kernel(
   }
 }
 
-template <bool PAGED>
+// KV = fp8: scale_log2 carries k_scale too, and every chunk length takes the 64-row kernel
+// (head-packed for short chunks): the 256-row kernel's tiles go global -> LDS by LDS-DMA,
+// with no register stage to convert in.
+template <bool PAGED, typename KV = u16>
 static int launch_prefill(void* out, int out_stride, const void* qkv, int row_stride,
                           const int* cu_seqlens, int num_seqs, int max_seqlen, int hq, int hkv,
                           int hd, float scale, const int* ctx_lens, const void* k_cache,
                           const void* v_cache, const int* block_tables, int bt_stride,
-                          int block_size, int window, hipStream_t st) {
+                          int block_size, int window, hipStream_t st, float k_scale = 1.f,
+                          [[maybe_unused]] float v_scale = 1.f) {
+  constexpr bool FP8 = sizeof(KV) == 1;
   if (num_seqs <= 0 || max_seqlen <= 0) return 0;
   if (window < 0) window = 0;
   if (hq % hkv || (hd != 64 && hd != 128)) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
-  if (hd == 128 && max_seqlen >= g_pl_min_len) {     // long sequences: 256-row workgroups
-    dim3 grid32((max_seqlen + PL_ROWS - 1) / PL_ROWS, num_seqs, hq);
-    prefill_attn32_kernel<128, PAGED><<<grid32, 512, 0, st>>>(
-        (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, window);
-    DLI_RETURN_LAUNCH();
+  const float sl2 = scale * 1.4426950408889634f * k_scale;       // (x 1 for a bf16 cache)
+  if constexpr (!FP8) {
+    if (hd == 128 && max_seqlen >= g_pl_min_len) {   // long sequences: 256-row workgroups
+      dim3 grid32((max_seqlen + PL_ROWS - 1) / PL_ROWS, num_seqs, hq);
+      prefill_attn32_kernel<128, PAGED><<<grid32, 512, 0, st>>>(
+          (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
+          (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, window);
+      DLI_RETURN_LAUNCH();
+    }
   }
   // waves per query head: pack 2 / 4 heads of one GQA group into a workgroup for short
   // prompts (the packed heads share their kv head, so G must be a multiple of the pack)
@@ -540,96 +547,51 @@ static int launch_prefill(void* out, int out_stride, const void* qkv, int row_st
   else if (g_pf_pack && max_seqlen <= 2 * PF_QROWS && G % 2 == 0) wph = 2;
   const int rows_per_wg = wph * PF_QROWS;
   dim3 grid((max_seqlen + rows_per_wg - 1) / rows_per_wg, num_seqs, hq * wph / PF_WAVES);
+  PrefillKvScale<FP8> kvs;
+  if constexpr (FP8) kvs.v_scale = v_scale;
   if (hd == 128)
-    prefill_attn_kernel<128, PAGED><<<grid, 256, 0, st>>>(
+    prefill_attn_kernel<128, PAGED, KV><<<grid, 256, 0, st>>>(
         (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph,
-        window, PrefillKvScale<false>{});
+        (const KV*)k_cache, (const KV*)v_cache, block_tables, bt_stride, block_size, wph,
+        window, kvs);
   else
-    prefill_attn_kernel<64, PAGED><<<grid, 256, 0, st>>>(
+    prefill_attn_kernel<64, PAGED, KV><<<grid, 256, 0, st>>>(
         (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const u16*)k_cache, (const u16*)v_cache, block_tables, bt_stride, block_size, wph,
-        window, PrefillKvScale<false>{});
+        (const KV*)k_cache, (const KV*)v_cache, block_tables, bt_stride, block_size, wph,
+        window, kvs);
   DLI_RETURN_LAUNCH();
 }
 
 // window > 0: sliding-window attention (query q sees keys q - window < j <= q)
-extern "C" int dli_prefill_attention_win(void* out, int out_stride, const void* qkv,
-                                         int row_stride, const int* cu_seqlens, int num_seqs,
-                                         int max_seqlen, int hq, int hkv, int hd, float scale,
-                                         int window, hipStream_t st) {
+extern "C" int dli_prefill_attention(void* out, int out_stride, const void* qkv, int row_stride,
+                                     const int* cu_seqlens, int num_seqs, int max_seqlen, int hq,
+                                     int hkv, int hd, float scale, int window, hipStream_t st) {
   return launch_prefill<false>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
                                max_seqlen, hq, hkv, hd, scale, nullptr, nullptr, nullptr,
                                nullptr, 0, 16, window, st);
 }
 
-extern "C" int dli_prefill_attention(void* out, int out_stride, const void* qkv, int row_stride,
-                                     const int* cu_seqlens, int num_seqs, int max_seqlen, int hq,
-                                     int hkv, int hd, float scale, hipStream_t st) {
-  return dli_prefill_attention_win(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
-                                   max_seqlen, hq, hkv, hd, scale, 0, st);
-}
-
 // Chunked prefill: q from qkv rows [cu[s], cu[s+1]); keys 0..ctx_lens[s]-1 of sequence s
 // from the paged caches [num_blocks, hkv, block_size, hd] through block_tables[s, :].
-extern "C" int dli_prefill_attention_paged_win(void* out, int out_stride, const void* qkv,
-                                               int row_stride, const int* cu_seqlens,
-                                               const int* ctx_lens, const void* k_cache,
-                                               const void* v_cache, const int* block_tables,
-                                               int bt_stride, int num_seqs, int max_seqlen,
-                                               int hq, int hkv, int hd, int block_size,
-                                               float scale, int window, hipStream_t st) {
-  if (block_size <= 0) return (int)hipErrorInvalidValue;
-  return launch_prefill<true>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
-                              max_seqlen, hq, hkv, hd, scale, ctx_lens, k_cache, v_cache,
-                              block_tables, bt_stride, block_size, window, st);
-}
-
+// kv_fp8: the caches hold e4m3fn bytes with the scales k_scale, v_scale (> 0); else bf16, 1.
 extern "C" int dli_prefill_attention_paged(void* out, int out_stride, const void* qkv,
                                            int row_stride, const int* cu_seqlens,
                                            const int* ctx_lens, const void* k_cache,
                                            const void* v_cache, const int* block_tables,
                                            int bt_stride, int num_seqs, int max_seqlen, int hq,
                                            int hkv, int hd, int block_size, float scale,
+                                           int window, int kv_fp8, float k_scale, float v_scale,
                                            hipStream_t st) {
-  return dli_prefill_attention_paged_win(out, out_stride, qkv, row_stride, cu_seqlens, ctx_lens,
-                                         k_cache, v_cache, block_tables, bt_stride, num_seqs,
-                                         max_seqlen, hq, hkv, hd, block_size, scale, 0, st);
-}
-
-// dli_prefill_attention_paged_win over an FP8 (e4m3fn) cache with the scales k_scale, v_scale
-// (> 0). Every chunk length takes the 64-row kernel (head-packed for short chunks): the
-// 256-row kernel's tiles go global -> LDS by LDS-DMA, with no register stage to convert in.
-extern "C" int dli_prefill_attention_paged_kv8(void* out, int out_stride, const void* qkv,
-                                               int row_stride, const int* cu_seqlens,
-                                               const int* ctx_lens, const void* k_cache,
-                                               const void* v_cache, const int* block_tables,
-                                               int bt_stride, int num_seqs, int max_seqlen,
-                                               int hq, int hkv, int hd, int block_size,
-                                               float scale, int window, float k_scale,
-                                               float v_scale, hipStream_t st) {
-  if (block_size <= 0 || !(k_scale > 0.f) || !(v_scale > 0.f)) return (int)hipErrorInvalidValue;
-  if (num_seqs <= 0 || max_seqlen <= 0) return 0;
-  if (window < 0) window = 0;
-  if (hq % hkv || (hd != 64 && hd != 128)) return (int)hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f * k_scale;
-  const int G = hq / hkv;
-  int wph = PF_WAVES;
-  if (g_pf_pack && max_seqlen <= PF_QROWS && G % 4 == 0) wph = 1;
-  else if (g_pf_pack && max_seqlen <= 2 * PF_QROWS && G % 2 == 0) wph = 2;
-  const int rows_per_wg = wph * PF_QROWS;
-  dim3 grid((max_seqlen + rows_per_wg - 1) / rows_per_wg, num_seqs, hq * wph / PF_WAVES);
-  if (hd == 128)
-    prefill_attn_kernel<128, true, fp8><<<grid, 256, 0, st>>>(
-        (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const fp8*)k_cache, (const fp8*)v_cache, block_tables, bt_stride, block_size, wph,
-        window, PrefillKvScale<true>{v_scale});
-  else
-    prefill_attn_kernel<64, true, fp8><<<grid, 256, 0, st>>>(
-        (u16*)out, out_stride, (const u16*)qkv, row_stride, cu_seqlens, hq, hkv, sl2, ctx_lens,
-        (const fp8*)k_cache, (const fp8*)v_cache, block_tables, bt_stride, block_size, wph,
-        window, PrefillKvScale<true>{v_scale});
-  DLI_RETURN_LAUNCH();
+  if (block_size <= 0 || !kv_scales_ok(kv_fp8, k_scale, v_scale))
+    return (int)hipErrorInvalidValue;
+  if (!kv_fp8)
+    return launch_prefill<true>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
+                                max_seqlen, hq, hkv, hd, scale, ctx_lens, k_cache, v_cache,
+                                block_tables, bt_stride, block_size, window, st);
+  return launch_prefill<true, fp8>(out, out_stride, qkv, row_stride, cu_seqlens, num_seqs,
+                                   max_seqlen, hq, hkv, hd, scale, ctx_lens, k_cache, v_cache,
+                                   block_tables, bt_stride, block_size, window, st, k_scale,
+                                   v_scale);
 }
 
 // 0 / 1: head packing of the short-prompt kernel off / on; returns the previous setting

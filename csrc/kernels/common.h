@@ -62,6 +62,12 @@ __device__ __forceinline__ void store8(u16* p, const float* f) {
 typedef uint8_t fp8;
 constexpr float FP8_E4M3_MAX = 448.f;
 
+// The (kv_fp8, scale, scale) tail of the cache writers and readers: an FP8 cache's scales (or
+// their inverses) are > 0 (a NaN fails), and only an FP8 cache has scales other than 1
+static inline bool kv_scales_ok(int kv_fp8, float k_scale, float v_scale) {
+  return kv_fp8 ? k_scale > 0.f && v_scale > 0.f : k_scale == 1.f && v_scale == 1.f;
+}
+
 // 8 fp32 -> 8 e4m3fn bytes (one 8-byte store; v_cvt_pk_fp8_f32 rounds to nearest even)
 __device__ __forceinline__ void store8_fp8(fp8* p, const float* f, float inv_scale) {
   float c[8];

@@ -4,7 +4,7 @@
 //  dli_splitk_add_rmsnorm : out = rmsnorm(residual += sum_s P_s) * w     (O-proj, down-proj)
 //                           (w == null: residual += sum_s P_s only, for a stage's last layer)
 //  dli_splitk_rope_cache  : qkv = bf16(sum_s P_s); RoPE on q,k in place; k,v -> paged cache
-//  dli_splitk_rope_cache_x: the same with a QKV bias and / or a per-head q,k RMSNorm (Qwen)
+//                           (with a QKV bias and / or a per-head q,k RMSNorm for Qwen)
 //
 // P_s are the [M, N] slabs written by a GEMM called with C == nullptr: fp32, or (fmt 1, the
 // EPI_SLAB16 epilogue of the MFMA families) fp16 scaled by 1/16. The sum is fp32 in slab
@@ -221,50 +221,6 @@ __global__ void __launch_bounds__(256) splitk_rope_cache_x_kernel(
                                       bias, q_norm_w, k_norm_w, qk_eps);
 }
 
-// bias / q_norm_w / k_norm_w: see qkv_extras_ok; all null = dli_splitk_rope_cache
-extern "C" int dli_splitk_rope_cache_x(void* qkv, const float* ws, int splits, int T, int N,
-                                       const int* positions, const int* slot_mapping,
-                                       const float* cos_sin, void* k_cache, void* v_cache,
-                                       int hq, int hkv, int hd, int block_size, int use_rope,
-                                       int fmt, const void* bias, const void* q_norm_w,
-                                       const void* k_norm_w, float qk_eps, hipStream_t st) {
-  if (T <= 0) return 0;
-  if (hd % 16 || N != (hq + 2 * hkv) * hd || fmt < 0 || fmt > 1 ||
-      (fmt == 1 && splits != 2 && splits != 4 && splits != 8))
-    return (int)hipErrorInvalidValue;
-  const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
-  const int blocks = (int)((total + 255) / 256);
-  const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
-  if (!qkv_extras_ok(bias, q_norm_w, k_norm_w, hd)) return (int)hipErrorInvalidValue;
-#define DLI_SRC(S, F)                                                                       \
-  do {                                                                                      \
-    if (extras)                                                                             \
-      splitk_rope_cache_x_kernel<S, F><<<blocks, 256, 0, st>>>(                             \
-          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (u16*)k_cache,     \
-          (u16*)v_cache, hq, hkv, hd, block_size, use_rope, (const u16*)bias,               \
-          (const u16*)q_norm_w, (const u16*)k_norm_w, qk_eps);                              \
-    else                                                                                    \
-      splitk_rope_cache_kernel<S, F><<<blocks, 256, 0, st>>>(                               \
-          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (u16*)k_cache,     \
-          (u16*)v_cache, hq, hkv, hd, block_size, use_rope);                                \
-  } while (0)
-  if (fmt == 1) {
-    switch (splits) {
-      case 2: DLI_SRC(2, QkvSrc::SLAB16); break;
-      case 4: DLI_SRC(4, QkvSrc::SLAB16); break;
-      default: DLI_SRC(8, QkvSrc::SLAB16);
-    }
-  } else {
-    switch (splits) {
-      case 2: DLI_SRC(2, QkvSrc::SLAB32); break;
-      case 4: DLI_SRC(4, QkvSrc::SLAB32); break;
-      default: DLI_SRC(0, QkvSrc::SLAB32);
-    }
-  }
-#undef DLI_SRC
-  DLI_RETURN_LAUNCH();
-}
-
 // The same slabs into an FP8 (e4m3fn) cache: see store8_fp8 of common.h
 template <int SPL, QkvSrc SRC, bool X>
 __global__ void __launch_bounds__(256) splitk_rope_cache_kv8_kernel(
@@ -280,59 +236,65 @@ __global__ void __launch_bounds__(256) splitk_rope_cache_kv8_kernel(
                                         v_inv_scale);
 }
 
-// dli_splitk_rope_cache_x with an FP8 cache; k_inv_scale / v_inv_scale as dli_rope_cache_kv8
-extern "C" int dli_splitk_rope_cache_kv8(void* qkv, const float* ws, int splits, int T, int N,
-                                         const int* positions, const int* slot_mapping,
-                                         const float* cos_sin, void* k_cache, void* v_cache,
-                                         int hq, int hkv, int hd, int block_size, int use_rope,
-                                         int fmt, const void* bias, const void* q_norm_w,
-                                         const void* k_norm_w, float qk_eps, float k_inv_scale,
-                                         float v_inv_scale, hipStream_t st) {
-  if (T <= 0) return 0;
-  if (hd % 16 || N != (hq + 2 * hkv) * hd || fmt < 0 || fmt > 1 || splits < 1 ||
-      (fmt == 1 && splits != 2 && splits != 4 && splits != 8) || !(k_inv_scale > 0.f) ||
-      !(v_inv_scale > 0.f))
-    return (int)hipErrorInvalidValue;
-  const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
-  const int blocks = (int)((total + 255) / 256);
-  const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
-  if (!qkv_extras_ok(bias, q_norm_w, k_norm_w, hd)) return (int)hipErrorInvalidValue;
-#define DLI_SRC8(S, F)                                                                      \
-  do {                                                                                      \
-    if (extras)                                                                             \
-      splitk_rope_cache_kv8_kernel<S, F, true><<<blocks, 256, 0, st>>>(                     \
-          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (fp8*)k_cache,     \
-          (fp8*)v_cache, hq, hkv, hd, block_size, use_rope, (const u16*)bias,               \
-          (const u16*)q_norm_w, (const u16*)k_norm_w, qk_eps, k_inv_scale, v_inv_scale);    \
-    else                                                                                    \
-      splitk_rope_cache_kv8_kernel<S, F, false><<<blocks, 256, 0, st>>>(                    \
-          (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (fp8*)k_cache,     \
-          (fp8*)v_cache, hq, hkv, hd, block_size, use_rope, nullptr, nullptr, nullptr, 0.f, \
-          k_inv_scale, v_inv_scale);                                                        \
-  } while (0)
-  if (fmt == 1) {
-    switch (splits) {
-      case 2: DLI_SRC8(2, QkvSrc::SLAB16); break;
-      case 4: DLI_SRC8(4, QkvSrc::SLAB16); break;
-      default: DLI_SRC8(8, QkvSrc::SLAB16);
-    }
-  } else {
-    switch (splits) {
-      case 2: DLI_SRC8(2, QkvSrc::SLAB32); break;
-      case 4: DLI_SRC8(4, QkvSrc::SLAB32); break;
-      default: DLI_SRC8(0, QkvSrc::SLAB32);
-    }
-  }
-#undef DLI_SRC8
-  DLI_RETURN_LAUNCH();
-}
-
+// fmt: 0 = fp32 slabs, 1 = fp16 x 1/16 slabs (EPI_SLAB16). bias / q_norm_w / k_norm_w: see
+// qkv_extras_ok; all null on a bf16 cache = the plain kernel. kv_fp8, k_inv_scale,
+// v_inv_scale: as dli_rope_cache.
 extern "C" int dli_splitk_rope_cache(void* qkv, const float* ws, int splits, int T, int N,
                                      const int* positions, const int* slot_mapping,
                                      const float* cos_sin, void* k_cache, void* v_cache, int hq,
                                      int hkv, int hd, int block_size, int use_rope, int fmt,
-                                     hipStream_t st) {
-  return dli_splitk_rope_cache_x(qkv, ws, splits, T, N, positions, slot_mapping, cos_sin,
-                                 k_cache, v_cache, hq, hkv, hd, block_size, use_rope, fmt,
-                                 nullptr, nullptr, nullptr, 0.f, st);
+                                     const void* bias, const void* q_norm_w,
+                                     const void* k_norm_w, float qk_eps, int kv_fp8,
+                                     float k_inv_scale, float v_inv_scale, hipStream_t st) {
+  if (T <= 0) return 0;
+  if (hd % 16 || N != (hq + 2 * hkv) * hd || fmt < 0 || fmt > 1 || splits < 1 ||
+      (fmt == 1 && splits != 2 && splits != 4 && splits != 8) ||
+      !kv_scales_ok(kv_fp8, k_inv_scale, v_inv_scale) ||
+      !qkv_extras_ok(bias, q_norm_w, k_norm_w, hd))
+    return (int)hipErrorInvalidValue;
+  const long total = (long)T * (hq + 2 * hkv) * (hd / 16);
+  const int blocks = (int)((total + 255) / 256);
+  const bool extras = bias != nullptr || q_norm_w != nullptr || k_norm_w != nullptr;
+  // one kernel per cache type x (slab count, source) x extras
+#define DLI_SRC_ARGS                                                                        \
+  (u16*)qkv, ws, splits, T, N, positions, slot_mapping, cos_sin, (KV*)k_cache, (KV*)v_cache, \
+      hq, hkv, hd, block_size, use_rope
+#define DLI_SRC_X (const u16*)bias, (const u16*)q_norm_w, (const u16*)k_norm_w, qk_eps
+#define DLI_SRC(S, F)                                                                       \
+  do {                                                                                      \
+    if constexpr (sizeof(KV) == 2) {                                                        \
+      if (extras)                                                                           \
+        splitk_rope_cache_x_kernel<S, F><<<blocks, 256, 0, st>>>(DLI_SRC_ARGS, DLI_SRC_X);  \
+      else                                                                                  \
+        splitk_rope_cache_kernel<S, F><<<blocks, 256, 0, st>>>(DLI_SRC_ARGS);               \
+    } else if (extras) {                                                                    \
+      splitk_rope_cache_kv8_kernel<S, F, true><<<blocks, 256, 0, st>>>(                     \
+          DLI_SRC_ARGS, DLI_SRC_X, k_inv_scale, v_inv_scale);                               \
+    } else {                                                                                \
+      splitk_rope_cache_kv8_kernel<S, F, false><<<blocks, 256, 0, st>>>(                    \
+          DLI_SRC_ARGS, DLI_SRC_X, k_inv_scale, v_inv_scale);                               \
+    }                                                                                       \
+  } while (0)
+  auto launch = [&](auto kv) {
+    using KV = decltype(kv);
+    if (fmt == 1) {
+      switch (splits) {
+        case 2: DLI_SRC(2, QkvSrc::SLAB16); break;
+        case 4: DLI_SRC(4, QkvSrc::SLAB16); break;
+        default: DLI_SRC(8, QkvSrc::SLAB16);
+      }
+    } else {
+      switch (splits) {
+        case 2: DLI_SRC(2, QkvSrc::SLAB32); break;
+        case 4: DLI_SRC(4, QkvSrc::SLAB32); break;
+        default: DLI_SRC(0, QkvSrc::SLAB32);
+      }
+    }
+  };
+  if (!kv_fp8) launch(u16{});
+  else launch(fp8{});
+#undef DLI_SRC
+#undef DLI_SRC_X
+#undef DLI_SRC_ARGS
+  DLI_RETURN_LAUNCH();
 }

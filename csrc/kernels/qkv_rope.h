@@ -29,7 +29,7 @@ __device__ __forceinline__ long kv_cache_row(int slot, int block_size, int hkv, 
   return (((long)blk * hkv + kvh) * block_size + off) * hd;
 }
 
-// bias / q_norm_w / k_norm_w of the *_x launchers: bf16, 16-B aligned, or null, the two norm
+// bias / q_norm_w / k_norm_w of the launchers: bf16, 16-B aligned, or null, the two norm
 // weights together; a normalised head's hd / 16 lanes must be a shuffle group
 static inline bool qkv_extras_ok(const void* bias, const void* q_norm_w, const void* k_norm_w,
                                  int hd) {

@@ -503,6 +503,8 @@ def _qkv_extras(bias, qk_norm, n: int, hd: int):
     """The optional inputs of the RoPE kernels, checked: ``bias`` [n] (Qwen2's QKV bias) and
     ``qk_norm`` = (q_w [hd], k_w [hd], eps) (Qwen3's per-head RMSNorm of q and k before the
     rotation). Returns (bias, q_w, k_w, eps) with None for what is absent."""
+    if bias is None and qk_norm is None:
+        return None, None, None, 0.0
     q_w = k_w = None
     eps = 0.0
     if qk_norm is not None:
@@ -543,6 +545,13 @@ def kv_cache_is_fp8(k_cache, v_cache, k_scale: float = 1.0, v_scale: float = 1.0
     return fp8
 
 
+def _kv_inv_scales(fp8: bool, k_scale: float, v_scale: float):
+    """The cache writers' (kv_fp8, 1 / k_scale, 1 / v_scale) arguments."""
+    if not fp8:
+        return 0, 1.0, 1.0
+    return 1, R.inv_scale(k_scale), R.inv_scale(v_scale)
+
+
 def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
                       use_rope: bool = True, plan: Optional[G.GemmPlan] = None, bias=None,
                       qk_norm=None, k_scale: float = 1.0, v_scale: float = 1.0):
@@ -573,22 +582,11 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
     fmt = _slab_gemm(x, w, p, ws)
     qkv = torch.empty(M, Nn, dtype=x.dtype, device=x.device)
     bs = k_cache.shape[2] if k_cache is not None else 16
-    if fp8:
-        bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
-        _native_call("dli_splitk_rope_cache_kv8", _p(qkv), _p(ws), p.splits, M, Nn,
-                     _p(positions), _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq,
-                     hkv, hd, bs, int(use_rope), fmt, _p(bias), _p(q_w), _p(k_w), eps,
-                     R.inv_scale(k_scale), R.inv_scale(v_scale), _st())
-        return qkv
-    if bias is None and qk_norm is None:
-        _native_call("dli_splitk_rope_cache", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
-                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq, hkv, hd, bs,
-                     int(use_rope), fmt, _st())
-        return qkv
     bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
-    _native_call("dli_splitk_rope_cache_x", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
+    _native_call("dli_splitk_rope_cache", _p(qkv), _p(ws), p.splits, M, Nn, _p(positions),
                  _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), hq, hkv, hd, bs,
-                 int(use_rope), fmt, _p(bias), _p(q_w), _p(k_w), eps, _st())
+                 int(use_rope), fmt, _p(bias), _p(q_w), _p(k_w), eps,
+                 *_kv_inv_scales(fp8, k_scale, v_scale), _st())
     return qkv
 
 
@@ -617,8 +615,7 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     span = decode_span(max_context, window)
     if decode_num_splits(B, hkv, span) != 1:
         return None
-    mode = int(N.require_native().dli_decode_get_pipe())
-    if mode == 1 or (mode == 2 and -(-span // 32) * 32 >= 768):
+    if N.require_native().dli_decode_uses_pipe(hd, span, 1):
         return None                       # dli_decode_attention picks the pipelined kernel
     Nn = w.shape[0]
     fmt = 0
@@ -633,14 +630,8 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
                 x = x.materialize()
             fmt = _slab_gemm(x, w, p, src)
     out = torch.empty(B, hq * hd, dtype=x.dtype, device=x.device)
-    if bias is None and qk_norm is None:
-        _native_call("dli_decode_attention_fused_win", _p(out), _p(src), splits, _p(positions),
-                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), _p(block_tables),
-                     block_tables.stride(0), _p(context_lens), B, hq, hkv, hd, k_cache.shape[2],
-                     scale, fmt, max(int(window), 0), _st())
-        return out
     bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
-    _native_call("dli_decode_attention_fused_x", _p(out), _p(src), splits, _p(positions),
+    _native_call("dli_decode_attention_fused", _p(out), _p(src), splits, _p(positions),
                  _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), _p(block_tables),
                  block_tables.stride(0), _p(context_lens), B, hq, hkv, hd, k_cache.shape[2],
                  scale, fmt, max(int(window), 0), _p(bias), _p(q_w), _p(k_w), eps, _st())
@@ -715,22 +706,10 @@ def rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, 
                                 v_scale=v_scale)
     T = qkv.shape[0]
     bs = k_cache.shape[2] if k_cache is not None else 16
-    if fp8:
-        bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, (hq + 2 * hkv) * hd, hd)
-        _native_call("dli_rope_cache_kv8", _p(qkv), qkv.stride(0), _p(positions),
-                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs,
-                     int(use_rope), _p(bias), _p(q_w), _p(k_w), eps, R.inv_scale(k_scale),
-                     R.inv_scale(v_scale), _st())
-        return R.split_qkv(qkv, hq, hkv, hd)
-    if bias is None and qk_norm is None:
-        _native_call("dli_rope_cache", _p(qkv), qkv.stride(0), _p(positions),
-                     _p(slot_mapping), _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs,
-                     int(use_rope), _st())
-        return R.split_qkv(qkv, hq, hkv, hd)
     bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, (hq + 2 * hkv) * hd, hd)
-    _native_call("dli_rope_cache_x", _p(qkv), qkv.stride(0), _p(positions), _p(slot_mapping),
+    _native_call("dli_rope_cache", _p(qkv), qkv.stride(0), _p(positions), _p(slot_mapping),
                  _p(cos_sin), _p(k_cache), _p(v_cache), T, hq, hkv, hd, bs, int(use_rope),
-                 _p(bias), _p(q_w), _p(k_w), eps, _st())
+                 _p(bias), _p(q_w), _p(k_w), eps, *_kv_inv_scales(fp8, k_scale, v_scale), _st())
     return R.split_qkv(qkv, hq, hkv, hd)
 
 
@@ -752,7 +731,7 @@ def prefill_attention(qkv, cu_seqlens, max_seqlen: int, hq, hkv, hd, scale, out=
     if out is None:
         out = torch.empty(T, hq * hd, dtype=qkv.dtype, device=qkv.device)
     nseq = cu_seqlens.shape[0] - 1
-    _native_call("dli_prefill_attention_win", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
+    _native_call("dli_prefill_attention", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
                  _p(cu_seqlens), nseq, max_seqlen, hq, hkv, hd, scale, window, _st())
     return out
 
@@ -807,16 +786,10 @@ def prefill_attention_paged(qkv, cu_seqlens, max_seqlen: int, context_lens, bloc
     if out is None:
         out = torch.empty(T, hq * hd, dtype=qkv.dtype, device=qkv.device)
     nseq = cu_seqlens.shape[0] - 1
-    if fp8:
-        _native_call("dli_prefill_attention_paged_kv8", _p(out), out.stride(0), _p(qkv),
-                     qkv.stride(0), _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache),
-                     _p(block_tables), block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd,
-                     k_cache.shape[2], scale, window, float(k_scale), float(v_scale), _st())
-        return out
-    _native_call("dli_prefill_attention_paged_win", _p(out), out.stride(0), _p(qkv),
-                 qkv.stride(0), _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache),
-                 _p(block_tables), block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd,
-                 k_cache.shape[2], scale, window, _st())
+    _native_call("dli_prefill_attention_paged", _p(out), out.stride(0), _p(qkv), qkv.stride(0),
+                 _p(cu_seqlens), _p(context_lens), _p(k_cache), _p(v_cache), _p(block_tables),
+                 block_tables.stride(0), nseq, max_seqlen, hq, hkv, hd, k_cache.shape[2], scale,
+                 window, int(fp8), float(k_scale), float(v_scale), _st())
     return out
 
 
@@ -865,18 +838,12 @@ def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_cont
         num_splits = decode_num_splits(B, hkv, decode_span(max_context, window))
     ws = None
     if num_splits > 1:
-        nbytes = B * hq * num_splits * (hd + 2) * 4
-        ws = G.workspace(qkv.device, nbytes)
-    bs = k_cache.shape[2]
-    if fp8:
-        _native_call("dli_decode_attention_kv8", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
-                     _p(v_cache), _p(block_tables), block_tables.stride(0), _p(context_lens), B,
-                     hq, hkv, hd, bs, scale, max_context, num_splits, _p(ws), window,
-                     float(k_scale), float(v_scale), _st())
-        return out
-    _native_call("dli_decode_attention_win", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
+        ws = G.workspace(qkv.device, int(N.require_native().dli_decode_attention_workspace_bytes(
+            B, hq, hd, num_splits)))
+    _native_call("dli_decode_attention", _p(out), _p(qkv), qkv.stride(0), _p(k_cache),
                  _p(v_cache), _p(block_tables), block_tables.stride(0), _p(context_lens), B, hq,
-                 hkv, hd, bs, scale, max_context, num_splits, _p(ws), window, _st())
+                 hkv, hd, k_cache.shape[2], scale, max_context, num_splits, _p(ws), window,
+                 int(fp8), float(k_scale), float(v_scale), _st())
     return out
 
 

@@ -33,28 +33,27 @@ _SIGS = {
     "dli_fused_add_rmsnorm": [P, P, P, P, I, I, F, P],
     "dli_layernorm": [P, P, P, P, P, I, I, F, P],
     "dli_fused_add_layernorm": [P, P, P, P, P, I, I, F, P],
-    "dli_rope_cache": [P, I, P, P, P, P, P, I, I, I, I, I, I, P],
+    # the QKV writers: ..., qkv bias, q_norm w, k_norm w, eps, kv_fp8, 1/k_scale, 1/v_scale, stream
+    "dli_rope_cache": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, I, F, F, P],
     "dli_embedding": [P, P, P, P, P, I, I, P],
     "dli_silu_mul": [P, P, I, I, P],
     "dli_bias_act": [P, P, I, I, I, P],
     "dli_feed_ids": [P, P, P, I, I, P],
     "dli_prefetch": [P, L, I, P, P],
-    "dli_decode_attention": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, P],
-    "dli_decode_attention_win": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, P],
+    # the paged-cache readers: ..., window, kv_fp8, k_scale, v_scale, stream
+    "dli_decode_attention": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, I, F, F, P],
     "dli_decode_attention_workspace_bytes": [I, I, I, I],
-    "dli_prefill_attention": [P, I, P, I, P, I, I, I, I, I, F, P],
-    "dli_prefill_attention_win": [P, I, P, I, P, I, I, I, I, I, F, I, P],
+    "dli_prefill_attention": [P, I, P, I, P, I, I, I, I, I, F, I, P],
     "dli_prefill_set_min_len": [I],
     "dli_prefill_set_pack": [I],
     "dli_sample_set_split_max_b": [I],
     "dli_decode_set_pipe": [I],
-    "dli_decode_get_pipe": [],
+    "dli_decode_uses_pipe": [I, I, I],
     "dli_decode_set_form": [I],
     "dli_gemm_set_slab_store": [I],
     "dli_gemm_set_slab_store_family": [I, I],
-    "dli_prefill_attention_paged": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, P],
-    "dli_prefill_attention_paged_win": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I,
-                                        P],
+    "dli_prefill_attention_paged": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I, I, F,
+                                    F, P],
     "dli_sample": [P, P, L, I, I, P, P, P, P, P, P],
     "dli_sample_workspace_bytes": [I, I],
     "dli_sample_bf16": [P, P, L, I, I, P, P, P, P, P, P],
@@ -63,23 +62,11 @@ _SIGS = {
     "dli_gemm": [P, I, P, I, P, I, I, I, I, I, I, I, P, P, P, I, P],
     "dli_splitk_add_rmsnorm": [P, P, P, I, I, I, P, F, I, P],
     "dli_gemv_fused": [P, I, P, F, P, I, P, I, I, I, I, I, I, I, P, P],
-    "dli_splitk_rope_cache": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P],
-    "dli_decode_attention_fused": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, P],
-    "dli_decode_attention_fused_win": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
-                                       P],
-    # the three RoPE kernels with the Qwen extras: ..., qkv bias, q_norm w, k_norm w, eps, stream
-    "dli_rope_cache_x": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, P],
-    "dli_splitk_rope_cache_x": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, P],
-    "dli_decode_attention_fused_x": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I,
-                                     P, P, P, F, P],
-    # FP8 (e4m3fn) KV cache: the two writers (..., extras, 1/k_scale, 1/v_scale, stream) and
-    # the two readers (..., window, k_scale, v_scale, stream)
-    "dli_rope_cache_kv8": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, F, F, P],
-    "dli_splitk_rope_cache_kv8": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, F,
-                                  F, P],
-    "dli_decode_attention_kv8": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, F, F, P],
-    "dli_prefill_attention_paged_kv8": [P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, I, F, I, F,
-                                        F, P],
+    "dli_splitk_rope_cache": [P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, F, I, F,
+                              F, P],
+    # ..., fmt, window, qkv bias, q_norm w, k_norm w, eps, stream
+    "dli_decode_attention_fused": [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, I, P,
+                                   P, P, F, P],
     # FP8 block-scaled weights: dli_gemm's GEMV case and dli_gemv_fused with the scales and
     # their row stride after the weight pointer; the bf16 image of a weight (q, s, out, N, K)
     "dli_gemv_fp8": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],

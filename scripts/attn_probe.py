@@ -80,10 +80,10 @@ def main():
         kv_mb = B * hkv * ops.decode_span(ctx, W) * 2 * hd * 2 / 1e6
 
         def fused():
-            ops._native_call("dli_decode_attention_fused_win", ops._p(out), ops._p(slabs), 2,
+            ops._native_call("dli_decode_attention_fused", ops._p(out), ops._p(slabs), 2,
                              ops._p(pos), ops._p(slot), ops._p(cos_sin), ops._p(kc), ops._p(vc),
                              ops._p(bt), bt.stride(0), ops._p(cl), B, hq, hkv, hd, bs, scale, 1,
-                             W, ops._st())
+                             W, None, None, None, 0.0, ops._st())
 
         def rope():
             ops.rope_and_cache(qkv, pos, slot, cos_sin, kc, vc, hq, hkv, hd)

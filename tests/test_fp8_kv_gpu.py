@@ -288,3 +288,53 @@ def test_fp8_graph_decode_equals_eager(gpu, name, monkeypatch):
         outs.append([o.output_ids for o in eng.generate(prompts, sp)])
         assert int(eng.kv.k.view(U8).max()) > 0
     assert outs[0] == outs[1]
+
+
+# ------------------------------------------------------------------------------ the kv_fp8 flag
+def entry_args(dev, kv_dtype):
+    """Valid arguments of the four entry points that take (kv_fp8, scale, scale), by name,
+    without that tail and the stream: one sequence of 5 tokens, 8 / 2 heads of 128, 2 slabs."""
+    hq, hkv, hd, bs, T = 8, 2, 128, 16, 5
+    n = (hq + 2 * hkv) * hd
+    qkv, ws = rnd(T, n, dev=dev), torch.zeros(2, T, n, device=dev)
+    out = torch.empty(T, hq * hd, dtype=BF, device=dev)
+    kc, vc = (torch.zeros(2, hkv, bs, hd, dtype=BF, device=dev).to(kv_dtype) for _ in range(2))
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)   # noqa: E731
+    pos, slots, cs = i32(list(range(T))), i32(list(range(T))), R.rope_cos_sin(16, hd, 1e4, dev)
+    tables, ctx, cu = i32([[1, 0]]), i32([T]), i32([0, T])
+    p = ops._p
+    keep = (qkv, ws, out, kc, vc, pos, slots, cs, tables, ctx, cu)
+    return keep, {
+        "dli_rope_cache": (p(qkv), n, p(pos), p(slots), p(cs), p(kc), p(vc), T, hq, hkv, hd, bs,
+                           1, None, None, None, 0.0),
+        "dli_splitk_rope_cache": (p(qkv), p(ws), 2, T, n, p(pos), p(slots), p(cs), p(kc), p(vc),
+                                  hq, hkv, hd, bs, 1, 0, None, None, None, 0.0),
+        "dli_decode_attention": (p(out), p(qkv), n, p(kc), p(vc), p(tables), 2, p(ctx), 1, hq,
+                                 hkv, hd, bs, hd ** -0.5, T, 1, None, 0),
+        "dli_prefill_attention_paged": (p(out), hq * hd, p(qkv), n, p(cu), p(ctx), p(kc), p(vc),
+                                        p(tables), 2, 1, T, hq, hkv, hd, bs, hd ** -0.5, 0),
+    }
+
+
+def test_bf16_cache_with_a_scale_is_refused(gpu):
+    """kv_fp8 = 0 with k_scale = 2: every entry point that takes the flag returns
+    hipErrorInvalidValue before any launch (``kv_cache_is_fp8`` keeps the ops from asking)."""
+    keep, calls = entry_args(gpu, BF)
+    for name, args in calls.items():
+        with pytest.raises(RuntimeError, match=f"{name} failed with hipError 1$"):
+            ops._native_call(name, *args, 0, 2.0, 1.0, ops._st())
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("kv_dtype", [BF, F8])
+def test_slab_writer_refuses_zero_splits(gpu, kv_dtype):
+    """splits = 0 is refused for either cache dtype, rows and caches untouched."""
+    keep, calls = entry_args(gpu, kv_dtype)
+    qkv, kc = keep[0], keep[3]
+    qkv0 = qkv.clone()
+    args = list(calls["dli_splitk_rope_cache"])
+    args[2] = 0
+    with pytest.raises(RuntimeError, match="dli_splitk_rope_cache failed with hipError 1$"):
+        ops._native_call("dli_splitk_rope_cache", *args, int(kv_dtype == F8), 1.0, 1.0, ops._st())
+    torch.cuda.synchronize()
+    assert torch.equal(qkv, qkv0) and int(kc.view(U8).max()) == 0

@@ -224,7 +224,7 @@ def test_fused_rope_attention_extras(gpu, request, monkeypatch, fused_case, wpi,
 # ------------------------------------------------------------------------------ null extras
 def test_null_extras_change_nothing(gpu, fused_case):
     """bias=None, qk_norm=None: the three ops give the bits of the calls that do not pass
-    them, and the new entry point with null pointers those of the old one."""
+    them, and the entry point called directly with null pointers gives them too."""
     c = fused_case
     B, N_ = c["B"], (HQ + 2 * HKV) * HD
     torch.manual_seed(44)
@@ -235,9 +235,9 @@ def test_null_extras_change_nothing(gpu, fused_case):
         ops.rope_and_cache(qkv, c["pos"], c["slots"], c["cs"], kc, vc, HQ, HKV, HD, **kw)
         res.append((qkv, kc, vc))
     qkv, kc, vc = qkv0.clone(), c["kc"].clone(), c["vc"].clone()
-    N.call("dli_rope_cache_x", qkv.data_ptr(), qkv.stride(0), c["pos"].data_ptr(),
+    N.call("dli_rope_cache", qkv.data_ptr(), qkv.stride(0), c["pos"].data_ptr(),
            c["slots"].data_ptr(), c["cs"].data_ptr(), kc.data_ptr(), vc.data_ptr(), B, HQ, HKV,
-           HD, BS, 1, None, None, None, 0.0, N.stream_ptr())
+           HD, BS, 1, None, None, None, 0.0, 0, 1.0, 1.0, N.stream_ptr())
     res.append((qkv, kc, vc))
     torch.cuda.synchronize()
     for other in res[1:]:
