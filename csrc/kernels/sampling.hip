@@ -37,8 +37,12 @@ __device__ __forceinline__ uint4 philox(uint2 key, uint4 ctr) {
   }
   return ctr;
 }
-__device__ __forceinline__ float u01(uint32_t x) {           // (0, 1)
-  return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+// (0, 1). (x >> 8) + 0.5 needs 25 bits from 2^23 up, so fp32 rounds it to even and 0xffffff
+// + 0.5 to 2^24: a uniform of exactly 1, whose Gumbel noise -log(-log 1) is +inf, and the
+// token wins whatever its logit (one draw in 2^24: one row in 130 at a 128k vocabulary).
+// Hence the clamp to the largest fp32 below 1.
+__device__ __forceinline__ float u01(uint32_t x) {
+  return fminf(((x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 struct ArgMax { float v; int i; };

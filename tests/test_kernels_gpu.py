@@ -795,8 +795,9 @@ def test_sampling_two_phase_matches_one_phase(gpu, B, V):
     torch.manual_seed(15)
     logits = torch.randn(B, V, device=gpu) * 3
     if B >= 2:                                 # 300 ties above everything else in one
-        logits[1, V // 3:V // 3 + 300] = 30.0  # chunk: it overflows -> full-row path (a
-        # whole row of ties is not used: the one-phase kernel keeps an arbitrary 2048 of them)
+        logits[1, V // 3:V // 3 + 300] = 30.0  # chunk: it overflows -> full-row path
+    if B >= 3:                                 # a whole row of ties: past 2048 the one-phase
+        logits[2] = 1.25                       # kernel keeps the lowest ids, as the chunks do
     lib = ops.N.require_native()
     ws = ops._sample_ws(logits.device, B, V)
     assert ws is not None
