@@ -184,7 +184,9 @@ class Fp8Weight:
     [N / 16, ceil(K / 128)], W[n, k] = float(q[n, k]) * scale[n // 16, k // 128]
     (``reference.dequantize_weight``). Looks like its [N, K] tensor to the planner (``shape``,
     ``dim()``, ``device``); the linear ops stream it through the FP8 GEMV kernels at
-    M <= ``G.GEMV_MAX_M`` and run every other shape on its bf16 image (``bf16()``)."""
+    M <= ``G.GEMV_MAX_M``, through the FP8 MFMA stream tiles up to ``G.FP8_STREAM_MAX_M`` rows
+    where the autotuner pinned one (``stream_ok``), and run every other shape on its bf16
+    image (``bf16()``)."""
     __slots__ = ("q", "scale")
     act_dtype = torch.bfloat16           # what the activations it meets are
 
@@ -255,6 +257,13 @@ class Fp8Weight:
         return (M <= G.GEMV_MAX_M and p.tile in G.GEMV_TILES and K % 16 == 0
                 and K % p.splits == 0 and (K // p.splits) % 16 == 0)
 
+    def stream_ok(self, M: int, p: G.GemmPlan) -> bool:
+        """Whether the FP8 MFMA weight stream (``dli_gemm_fp8_stream``) takes this call: one
+        of its tiles, ``G.GEMV_MAX_M`` < M <= ``G.FP8_STREAM_MAX_M``, K in whole 16-element
+        chunks and, with split-K, every slice a multiple of 128 (``G.stream_slices_ok``)."""
+        return (p.tile in G.FP8_STREAM_TILES and G.GEMV_MAX_M < M <= G.FP8_STREAM_MAX_M
+                and G.stream_slices_ok(self.q.shape[1], p.splits))
+
 
 def _dense(w):
     """The tensor the bf16 kernels (or, off the GPU, the reference ops) read for ``w``."""
@@ -265,6 +274,20 @@ def _dense(w):
 
 def _inner_contig(w) -> bool:
     return isinstance(w, Fp8Weight) or w.stride(-1) == 1
+
+
+def _stream_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> bool:
+    """Whether ``p`` runs this call on the FP8 MFMA weight stream (never ``w.bf16()``). A
+    stream tile forced on a plain tensor is an error; an ``Fp8Weight`` call the kernel cannot
+    take (``stream_ok``, rows not 16-B aligned, ``form_ok`` False: a grouped call or an
+    epilogue it has not) is False, and the caller falls back to the heuristic plan."""
+    if p.tile not in G.FP8_STREAM_TILES:
+        return False
+    if not isinstance(w, Fp8Weight):
+        raise ValueError(f"GEMM tile {p.tile} streams FP8 block-scaled weights "
+                         f"(ops.Fp8Weight) only, got a {w.dtype} tensor")
+    return (form_ok and w.stream_ok(x.shape[0], p) and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0)
 
 
 def deferred_norm_ok(x: torch.Tensor) -> bool:
@@ -355,6 +378,13 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
             plan = G.plan(M, Nn, K, epi, G.wdt(w))
         else:
             plan = G.grouped_plan(M, Nn, K, epi, groups)
+    stream = _stream_plan(x, w, plan, epi in G.FP8_STREAM_EPIS and group_off is None)
+    if plan.tile in G.FP8_STREAM_TILES and not stream:
+        # a stream plan this call cannot take (a cached plan met another M, an odd K): the
+        # heuristic plan on the dequantised image; the tile id never reaches dli_gemm
+        plan = (G._heuristic(M, Nn, K, epi) if group_off is None
+                else G.GemmPlan("dli", G.grouped_tile(M, groups), 1))
+        w = w.bf16()
     out_n = Nn // 2 if epi == "silu_mul" else Nn
     if out is None:
         dt = torch.float32 if epi == "f32" else x.dtype
@@ -365,6 +395,11 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
         ws = G.workspace(x.device, splits * M * Nn * 4)
     m_arg = M if group_off is None else rows_per_group
     if isinstance(w, Fp8Weight):
+        if stream:
+            _native_call("dli_gemm_fp8_stream", _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                         w.scale.stride(0), K, _p(out), out.stride(0), M, Nn, K, G.EPI[epi],
+                         plan.tile, splits, _p(bias), _p(ws), _st())
+            return out
         if (group_off is None and w.gemv_ok(M, plan)
                 and epi in ("none", "f32", "silu_mul", "bias", "splitk")):
             _native_call("dli_gemv_fp8", _p(x), x.stride(0), _p(w.q), _p(w.scale),
@@ -422,6 +457,16 @@ def _slab_gemm(x, w, p: G.GemmPlan, ws) -> int:
     (the MFMA families' EPI "slab16" store, half the bytes), 0 = fp32."""
     M, K = x.shape
     Nn = w.shape[0]
+    if _stream_plan(x, w, p):            # the FP8 stream tiles write fp32 slabs (fmt 0)
+        _native_call("dli_gemm_fp8_stream", _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                     w.scale.stride(0), K, None, Nn, M, Nn, K, 0, p.tile, p.splits, None,
+                     _p(ws), _st())
+        return 0
+    if p.tile in G.FP8_STREAM_TILES:
+        # a stream plan this call cannot take: the heuristic's tile on the dequantised image,
+        # at the split count the consumer was sized for
+        p = G.GemmPlan("dli", G._heuristic(M, Nn, K, "splitk").tile, p.splits)
+        w = w.bf16()
     fmt = 1 if (G.SLAB16 and p.tile in G.SLAB16_TILES and p.splits in (2, 4, 8)) else 0
     if isinstance(w, Fp8Weight):
         if w.gemv_ok(M, p):              # GEMV tiles write fp32 slabs (fmt 0)

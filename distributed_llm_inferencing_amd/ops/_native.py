@@ -72,6 +72,8 @@ _SIGS = {
     "dli_gemv_fp8": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
     "dli_gemv_fused_fp8": [P, I, P, F, P, P, I, I, P, I, I, I, I, I, I, I, P, P],
     "dli_dequant_fp8_block": [P, P, P, I, I, P],
+    # the FP8 weight stream at 4 < M <= 64 (MFMA tiles 70 / 71): dli_gemv_fp8's arguments
+    "dli_gemm_fp8_stream": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
     "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],
