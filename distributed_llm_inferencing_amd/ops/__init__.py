@@ -277,10 +277,10 @@ def _inner_contig(w) -> bool:
 
 
 def _stream_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> bool:
-    """Whether ``p`` runs this call on the FP8 MFMA weight stream (never ``w.bf16()``). A
-    stream tile forced on a plain tensor is an error; an ``Fp8Weight`` call the kernel cannot
-    take (``stream_ok``, rows not 16-B aligned, ``form_ok`` False: a grouped call or an
-    epilogue it has not) is False, and the caller falls back to the heuristic plan."""
+    """Whether ``p`` runs this call on the FP8 MFMA weight stream (``_pick_kernel``'s first
+    question; never ``w.bf16()``). A stream tile forced on a plain tensor is an error; an
+    ``Fp8Weight`` call the kernel cannot take (``stream_ok``, rows not 16-B aligned,
+    ``form_ok`` False: a grouped call or an epilogue it has not) is False."""
     if p.tile not in G.FP8_STREAM_TILES:
         return False
     if not isinstance(w, Fp8Weight):
@@ -288,6 +288,78 @@ def _stream_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> bool:
                          f"(ops.Fp8Weight) only, got a {w.dtype} tensor")
     return (form_ok and w.stream_ok(x.shape[0], p) and x.stride(0) % 8 == 0
             and x.data_ptr() % 16 == 0)
+
+
+def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
+                 keep_splits: bool = False):
+    """The one choice of a GEMM's native family: (kind, plan, weight) with kind "stream"
+    (``w`` an ``Fp8Weight`` on the MFMA weight stream), "gemv_fp8" (on the FP8 GEMV stream) or
+    "gemm" (``w`` a plain tensor: the bf16 image of an ``Fp8Weight`` neither stream takes,
+    dequantised here, once). A stream plan the call cannot take (a cached plan met another M,
+    an odd K, a grouped call) gives way to a plan of the bf16 families, so its tile id never
+    reaches ``dli_gemm``: the heuristic plan; with ``keep_splits`` (slabs a fused consumer was
+    sized for) the heuristic's tile at ``p``'s split count; ``grouped_tile`` for a grouped
+    call (``groups`` given)."""
+    fp8 = isinstance(w, Fp8Weight)
+    if not fp8 and p.tile not in G.FP8_STREAM_TILES:
+        return "gemm", p, w
+    M, K = x.shape
+    fp8_form = groups is None and epi in G.FP8_STREAM_EPIS
+    if _stream_plan(x, w, p, fp8_form):
+        return "stream", p, w
+    if p.tile in G.FP8_STREAM_TILES:
+        if groups is not None:
+            p = G.GemmPlan("dli", G.grouped_tile(M, groups), 1)
+        elif keep_splits:
+            p = G.GemmPlan("dli", G._heuristic(M, w.shape[-2], K, "splitk").tile, p.splits)
+        else:
+            p = G._heuristic(M, w.shape[-2], K, epi)
+    elif fp8_form and w.gemv_ok(M, p):
+        return "gemv_fp8", p, w
+    return "gemm", p, w.bf16()
+
+
+def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: int, Nn: int,
+                 K: int, bias=None, ws=None, group_off=None, groups: int = 1, tile_list=None,
+                 arow=None):
+    """Marshal one GEMM of ``_pick_kernel``'s ``kind``: C [rows, Nn] (None: slabs only, into
+    ``ws``) = epilogue ``code`` of x @ w.T. For "gemm", ``tile_list`` (list, max items) selects
+    the compact grouped grid and ``arow`` the row permutation x is read through."""
+    # the optional operands are None more often than not: no ``_p`` call for those
+    pC = None if C is None else _p(C)
+    pbias = None if bias is None else _p(bias)
+    poff = None if group_off is None else _p(group_off)
+    if kind != "gemm":
+        _native_call("dli_gemm_fp8_stream" if kind == "stream" else "dli_gemv_fp8", _p(x),
+                     x.stride(0), _p(w.q), _p(w.scale), w.scale.stride(0), K, pC, ldc, rows, Nn,
+                     K, code, p.tile, p.splits, pbias, _p(ws), _st())
+    elif tile_list is not None:
+        _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), pC, ldc,
+                     rows, Nn, K, code, p.tile, p.splits, _p(arow), _p(ws), poff, groups,
+                     _p(tile_list[0]), tile_list[1], _st())
+    elif arow is not None:               # unsplit SiLU*up only (G.GATHER_TILES)
+        _native_call("dli_gemm_grouped_gather", _p(x), x.stride(0), _p(w), w.stride(-2), pC, ldc,
+                     rows, Nn, K, p.tile, _p(arow), poff, groups, _st())
+    else:
+        _native_call("dli_gemm", _p(x), x.stride(0), _p(w), w.stride(-2), pC, ldc, rows, Nn, K,
+                     code, p.tile, p.splits, pbias, _p(ws), poff, groups, _st())
+
+
+def _launch_gemv_fused(rows, norm_w, eps: float, w, C, ldc: int, code: int, tile: int,
+                       splits: int, ws):
+    """Marshal the fused GEMV of either weight format: C = epilogue ``code`` of
+    (rmsnorm(rows) * norm_w, or ``rows`` as they are when ``norm_w`` is None) @ w.T."""
+    M, K = rows.shape
+    fp8 = isinstance(w, Fp8Weight)
+    wargs = (_p(w.q), _p(w.scale), w.scale.stride(0), K) if fp8 else (_p(w), w.stride(-2))
+    _native_call("dli_gemv_fused_fp8" if fp8 else "dli_gemv_fused", _p(rows), rows.stride(0),
+                 _p(norm_w), eps, *wargs, _p(C), ldc, M, w.shape[0], K, code, tile, splits,
+                 _p(ws), _st())
+
+
+def _out_width(n: int, epi: str) -> int:
+    """Columns of epi(x @ w.T) for an ``n``-row w: SiLU*up halves the interleaved gate/up rows."""
+    return n // 2 if epi == "silu_mul" else n
 
 
 def deferred_norm_ok(x: torch.Tensor) -> bool:
@@ -305,27 +377,20 @@ def _gemv_prologue(x: NormedRows, w, epi: str, plan: Optional[G.GemmPlan], C, ld
     tiles = G.GEMV_PRO_TILES.get(epi, ())
     if p.tile not in tiles or (p.tile in G.GEMV_PRO_M1_ONLY and M > 1) or M > G.GEMV_MAX_M:
         return False
-    r = x.residual
-    code = G.EPI["silu_mul"] if epi == "silu_mul" else 0
     if isinstance(w, Fp8Weight) and not w.gemv_ok(M, p):
         return False
+    r = x.residual
     if ws is None and p.splits > 1:      # split K into C: slabs + the reduce kernel
         ws = G.workspace(r.device, p.splits * M * w.shape[0] * 4)
-    if isinstance(w, Fp8Weight):
-        _native_call("dli_gemv_fused_fp8", _p(r), r.stride(0), _p(x.w), x.eps, _p(w.q),
-                     _p(w.scale), w.scale.stride(0), K, _p(C), ldc, M, w.shape[0], K, code,
-                     p.tile, p.splits, _p(ws), _st())
-        return True
-    _native_call("dli_gemv_fused", _p(r), r.stride(0), _p(x.w), x.eps, _p(w), w.stride(-2),
-                 _p(C), ldc, M, w.shape[0], K, code, p.tile, p.splits, _p(ws), _st())
+    _launch_gemv_fused(r, x.w, x.eps, w, C, ldc, G.EPI["silu_mul"] if epi == "silu_mul" else 0,
+                       p.tile, p.splits, ws)
     return True
 
 
 def linear_normed(x: NormedRows, w, epi: str, plan: G.GemmPlan):
     """epi(rmsnorm(x) @ w.T) under a forced plan (the autotuner's timing of a prologue GEMV;
     plans without a prologue variant materialise the norm first, as ``linear`` does)."""
-    n_out = w.shape[-2] // 2 if epi == "silu_mul" else w.shape[-2]
-    y = torch.empty(x.shape[0], n_out, dtype=x.dtype, device=x.device)
+    y = torch.empty(x.shape[0], _out_width(w.shape[-2], epi), dtype=x.dtype, device=x.device)
     if plan.splits > 1 and epi == "splitk":
         return _gemm_native(x.materialize(), w, "none", plan=plan)
     if _gemv_prologue(x, w, epi, plan, y, y.stride(0)):
@@ -344,13 +409,8 @@ def linear_residual(x, w, residual, plan: Optional[G.GemmPlan] = None):
             or (isinstance(w, Fp8Weight) and not w.gemv_ok(M, p))):
         linear_add_rmsnorm(x, w, residual, None, 0.0)
         return
-    if isinstance(w, Fp8Weight):
-        _native_call("dli_gemv_fused_fp8", _p(x), x.stride(0), None, 0.0, _p(w.q), _p(w.scale),
-                     w.scale.stride(0), K, _p(residual), residual.stride(0), M, w.shape[0], K,
-                     16, p.tile, 1, None, _st())
-        return
-    _native_call("dli_gemv_fused", _p(x), x.stride(0), None, 0.0, _p(w), w.stride(-2),
-                 _p(residual), residual.stride(0), M, w.shape[0], K, 16, p.tile, 1, None, _st())
+    _launch_gemv_fused(x, None, 0.0, w, residual, residual.stride(0), G.EPI_RES, p.tile, 1,
+                       None)
 
 
 # ----------------------------------------------------------------------------- embedding
@@ -373,48 +433,17 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
     then the total permuted rows."""
     M, K = x.shape
     Nn = w.shape[-2]
+    grouped = group_off is not None
     if plan is None:
-        if group_off is None:
-            plan = G.plan(M, Nn, K, epi, G.wdt(w))
-        else:
-            plan = G.grouped_plan(M, Nn, K, epi, groups)
-    stream = _stream_plan(x, w, plan, epi in G.FP8_STREAM_EPIS and group_off is None)
-    if plan.tile in G.FP8_STREAM_TILES and not stream:
-        # a stream plan this call cannot take (a cached plan met another M, an odd K): the
-        # heuristic plan on the dequantised image; the tile id never reaches dli_gemm
-        plan = (G._heuristic(M, Nn, K, epi) if group_off is None
-                else G.GemmPlan("dli", G.grouped_tile(M, groups), 1))
-        w = w.bf16()
-    out_n = Nn // 2 if epi == "silu_mul" else Nn
+        plan = (G.grouped_plan(M, Nn, K, epi, groups) if grouped
+                else G.plan(M, Nn, K, epi, G.wdt(w)))
+    kind, plan, w = _pick_kernel(x, w, plan, epi, groups if grouped else None)
     if out is None:
         dt = torch.float32 if epi == "f32" else x.dtype
-        out = torch.empty(M, out_n, dtype=dt, device=x.device)
-    splits = plan.splits
-    ws = None
-    if splits > 1:
-        ws = G.workspace(x.device, splits * M * Nn * 4)
-    m_arg = M if group_off is None else rows_per_group
-    if isinstance(w, Fp8Weight):
-        if stream:
-            _native_call("dli_gemm_fp8_stream", _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                         w.scale.stride(0), K, _p(out), out.stride(0), M, Nn, K, G.EPI[epi],
-                         plan.tile, splits, _p(bias), _p(ws), _st())
-            return out
-        if (group_off is None and w.gemv_ok(M, plan)
-                and epi in ("none", "f32", "silu_mul", "bias", "splitk")):
-            _native_call("dli_gemv_fp8", _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                         w.scale.stride(0), K, _p(out), out.stride(0), M, Nn, K, G.EPI[epi],
-                         plan.tile, splits, _p(bias), _p(ws), _st())
-            return out
-        w = w.bf16()
-    if tile_list is not None:
-        _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), _p(out),
-                     out.stride(0), m_arg, Nn, K, G.EPI[epi], plan.tile, splits, None, _p(ws),
-                     _p(group_off), groups, _p(tile_list[0]), tile_list[1], _st())
-        return out
-    _native_call("dli_gemm", _p(x), x.stride(0), _p(w), w.stride(-2), _p(out), out.stride(0),
-                 m_arg, Nn, K, G.EPI[epi], plan.tile, splits, _p(bias), _p(ws), _p(group_off),
-                 groups, _st())
+        out = torch.empty(M, _out_width(Nn, epi), dtype=dt, device=x.device)
+    ws = G.workspace(x.device, plan.splits * M * Nn * 4) if plan.splits > 1 else None
+    _launch_gemm(kind, x, w, plan, G.EPI[epi], out, out.stride(0),
+                 rows_per_group if grouped else M, Nn, K, bias, ws, group_off, groups, tile_list)
     return out
 
 
@@ -426,9 +455,8 @@ def linear(x, w, bias=None, epi: str = "none", out=None):
     if isinstance(x, NormedRows):
         if (bias is None and epi in ("none", "silu_mul") and _use_native(x.residual)
                 and x.residual.is_contiguous()):
-            M = x.shape[0]
-            n_out = w.shape[-2] // 2 if epi == "silu_mul" else w.shape[-2]
-            y = out if out is not None else torch.empty(M, n_out, dtype=x.dtype, device=x.device)
+            y = out if out is not None else torch.empty(x.shape[0], _out_width(w.shape[-2], epi),
+                                                        dtype=x.dtype, device=x.device)
             if _gemv_prologue(x, w, epi, None, y, y.stride(0)):
                 return y
         x = x.materialize()
@@ -451,42 +479,47 @@ def linear(x, w, bias=None, epi: str = "none", out=None):
     return _gemm_native(x, w, epi, bias=bias, out=out)
 
 
-def _slab_gemm(x, w, p: G.GemmPlan, ws) -> int:
-    """x @ w.T as ``p.splits`` split-K partial slabs in ``ws`` (no output tensor: a fused
-    consumer reduces them). Returns the slab format the consumer must read: 1 = fp16 x 1/16
-    (the MFMA families' EPI "slab16" store, half the bytes), 0 = fp32."""
-    M, K = x.shape
-    Nn = w.shape[0]
-    if _stream_plan(x, w, p):            # the FP8 stream tiles write fp32 slabs (fmt 0)
-        _native_call("dli_gemm_fp8_stream", _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                     w.scale.stride(0), K, None, Nn, M, Nn, K, 0, p.tile, p.splits, None,
-                     _p(ws), _st())
-        return 0
-    if p.tile in G.FP8_STREAM_TILES:
-        # a stream plan this call cannot take: the heuristic's tile on the dequantised image,
-        # at the split count the consumer was sized for
-        p = G.GemmPlan("dli", G._heuristic(M, Nn, K, "splitk").tile, p.splits)
-        w = w.bf16()
-    fmt = 1 if (G.SLAB16 and p.tile in G.SLAB16_TILES and p.splits in (2, 4, 8)) else 0
-    if isinstance(w, Fp8Weight):
-        if w.gemv_ok(M, p):              # GEMV tiles write fp32 slabs (fmt 0)
-            _native_call("dli_gemv_fp8", _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                         w.scale.stride(0), K, None, Nn, M, Nn, K, 0, p.tile, p.splits, None,
-                         _p(ws), _st())
-            return fmt
-        w = w.bf16()
-    _native_call("dli_gemm", _p(x), x.stride(0), _p(w), w.stride(-2), None, Nn, M, Nn, K,
-                 G.EPI["slab16"] if fmt else 0, p.tile, p.splits, None, _p(ws), None, 1, _st())
-    return fmt
-
-
 def _splitk_plan(x, w):
     """A split-K plan for a GEMM whose partial sums feed a fused reduce, or None."""
-    if not _use_native(x) or x.stride(-1) != 1 or not _inner_contig(w):
+    if not _use_native(x) or x.stride(-1) != 1 or not (isinstance(w, Fp8Weight)
+                                                       or w.stride(-1) == 1):
         return None
     M, K = x.shape
     p = G.plan(M, w.shape[0], K, "splitk", G.wdt(w))
     return p if p.splits > 1 else None
+
+
+def _split_slabs(x, w, plan: Optional[G.GemmPlan] = None, ws=None):
+    """The GEMM of a fused split-K consumer: (plan, workspace, slab format) with x @ w.T as
+    the plan's split-K partial slabs in the workspace (no output tensor: the consumer reduces
+    them), or None where the plan (``plan`` if forced, else the "splitk" plan of the shape)
+    does not split. The format the consumer must read: 1 = fp16 x 1/16 (the MFMA families'
+    EPI "slab16" store, half the bytes), 0 = fp32 (the GEMV and FP8 stream tiles, the 4-wave
+    family). ``x`` may be a ``NormedRows``: the GEMV with the norm in its prologue where the
+    plan has one, else the materialised norm. ``ws``: the caller's own slab buffer."""
+    normed = isinstance(x, NormedRows)
+    rows = x.residual if normed else x
+    p = _splitk_plan(rows, w) if plan is None else plan
+    if p is None or (p.splits == 1 and ws is None):
+        return None
+    M, K = rows.shape
+    Nn = w.shape[0]
+    if ws is None:
+        ws = G.workspace(rows.device, p.splits * M * Nn * 4)
+    if normed:
+        if _gemv_prologue(x, w, "splitk", p, None, Nn, ws=ws):
+            return p, ws, 0
+        x = x.materialize()
+    kind, run, w = _pick_kernel(x, w, p, "splitk", None, True)     # (keeps p's split count)
+    fmt = 1 if (G.SLAB16 and run.tile in G.SLAB16_TILES and run.splits in (2, 4, 8)) else 0
+    _launch_gemm(kind, x, w, run, G.EPI["slab16"] if fmt else 0, None, Nn, M, Nn, K, None, ws)
+    return p, ws, fmt
+
+
+def _slab_gemm(x, w, p: G.GemmPlan, ws) -> int:
+    """x @ w.T as ``p.splits`` split-K partial slabs in ``ws``; returns their format
+    (``_split_slabs``)."""
+    return _split_slabs(x, w, p, ws)[2]
 
 
 def linear_add_rmsnorm(x, w, residual, norm_w, eps, plan: Optional[G.GemmPlan] = None,
@@ -499,49 +532,35 @@ def linear_add_rmsnorm(x, w, residual, norm_w, eps, plan: Optional[G.GemmPlan] =
     rows — returns (out, topk_w, topk_ids); with fp16 slabs, N = 4096, E <= 8 and renormalised
     weights inside the same reduce kernel (``dli_splitk_add_rmsnorm_route``), else by
     ``moe_router``."""
-    if route is not None:
-        wr, k = route[:2]
-        norm_topk = route[2] if len(route) > 2 else True
-        p = _splitk_plan(x, w) if plan is None else (plan if plan.splits > 1 else None)
-        M, K = x.shape
-        Nn = w.shape[0]
-        if (p is not None and norm_w is not None and Nn == 4096 and wr.shape[0] <= 8
-                and norm_topk and wr.is_contiguous() and residual.is_contiguous()
-                and wr.data_ptr() % 16 == 0):
-            ws = G.workspace(x.device, p.splits * M * Nn * 4)
-            fmt = _slab_gemm(x, w, p, ws)
-            if fmt == 1:
-                out = torch.empty_like(residual)
-                tw = torch.empty(M, k, dtype=torch.float32, device=x.device)
-                ti = torch.empty(M, k, dtype=torch.int32, device=x.device)
-                _native_call("dli_splitk_add_rmsnorm_route", _p(out), _p(residual), _p(ws),
-                             p.splits, M, Nn, _p(norm_w), eps, _p(wr), wr.shape[0], k, _p(tw),
-                             _p(ti), _st())
-                return out, tw, ti
-            out = torch.empty_like(residual)
-            _native_call("dli_splitk_add_rmsnorm", _p(out), _p(residual), _p(ws), p.splits, M,
-                         Nn, _p(norm_w), eps, fmt, _st())
-        else:
-            out = linear_add_rmsnorm(x, w, residual, norm_w, eps, plan=plan)
-        return (out,) + tuple(moe_router(out, wr, k, norm_topk))
-    if plan is None:
-        p = _splitk_plan(x, w)
-    else:
-        p = plan if plan.splits > 1 else None
-    if p is None:
+    slabs = _split_slabs(x, w, plan)
+    if slabs is None:
         y = linear(x, w) if plan is None else _gemm_native(x, w, "none", plan=plan)
         if norm_w is None:
             residual.add_(y)             # bf16 add computes in fp32 and rounds once
-            return None
-        return add_rmsnorm(y, residual, norm_w, eps)
-    M, K = x.shape
-    Nn = w.shape[0]
-    ws = G.workspace(x.device, p.splits * M * Nn * 4)
-    out = torch.empty_like(residual) if norm_w is not None else None
-    fmt = _slab_gemm(x, w, p, ws)
-    _native_call("dli_splitk_add_rmsnorm", _p(out), _p(residual), _p(ws), p.splits, M, Nn,
-                 _p(norm_w), eps, fmt, _st())
-    return out
+            out = None
+        else:
+            out = add_rmsnorm(y, residual, norm_w, eps)
+    else:
+        p, ws, fmt = slabs
+        M, Nn = residual.shape
+        out = torch.empty_like(residual) if norm_w is not None else None
+        if (route is not None and fmt == 1 and norm_w is not None and Nn == 4096
+                and route[0].shape[0] <= 8 and (len(route) < 3 or route[2])
+                and route[0].is_contiguous() and residual.is_contiguous()
+                and route[0].data_ptr() % 16 == 0):
+            wr, k = route[:2]
+            tw = torch.empty(M, k, dtype=torch.float32, device=x.device)
+            ti = torch.empty(M, k, dtype=torch.int32, device=x.device)
+            _native_call("dli_splitk_add_rmsnorm_route", _p(out), _p(residual), _p(ws),
+                         p.splits, M, Nn, _p(norm_w), eps, _p(wr), wr.shape[0], k, _p(tw),
+                         _p(ti), _st())
+            return out, tw, ti
+        _native_call("dli_splitk_add_rmsnorm", _p(out), _p(residual), _p(ws), p.splits, M, Nn,
+                     _p(norm_w), eps, fmt, _st())
+    if route is None:
+        return out
+    return (out,) + tuple(moe_router(out, route[0], route[1], route[2] if len(route) > 2
+                                     else True))
 
 
 def _qkv_extras(bias, qk_norm, n: int, hd: int):
@@ -609,11 +628,8 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
     fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(xr))
     if isinstance(x, NormedRows):
         x = x.materialize()
-    if plan is None:
-        p = _splitk_plan(x, w)
-    else:
-        p = plan if plan.splits > 1 else None
-    if p is None:
+    slabs = _split_slabs(x, w, plan)
+    if slabs is None:
         if plan is None:
             qkv = linear(x, w, bias)
         else:
@@ -621,10 +637,8 @@ def linear_rope_cache(x, w, positions, slot_mapping, cos_sin, k_cache, v_cache, 
         rope_and_cache(qkv, positions, slot_mapping, cos_sin, k_cache, v_cache, hq, hkv, hd,
                        use_rope, qk_norm=qk_norm, k_scale=k_scale, v_scale=v_scale)
         return qkv
-    M, K = x.shape
-    Nn = w.shape[0]
-    ws = G.workspace(x.device, p.splits * M * Nn * 4)
-    fmt = _slab_gemm(x, w, p, ws)
+    p, ws, fmt = slabs
+    M, Nn = x.shape[0], w.shape[0]
     qkv = torch.empty(M, Nn, dtype=x.dtype, device=x.device)
     bs = k_cache.shape[2] if k_cache is not None else 16
     bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
@@ -663,17 +677,11 @@ def linear_rope_attention(x, w, positions, slot_mapping, cos_sin, k_cache, v_cac
     if N.require_native().dli_decode_uses_pipe(hd, span, 1):
         return None                       # dli_decode_attention picks the pipelined kernel
     Nn = w.shape[0]
-    fmt = 0
     if p is None:                         # unsplit plan: the prologue reads the bf16 rows
-        src, splits = linear(x, w, bias), 0
+        src, splits, fmt = linear(x, w, bias), 0, 0
         bias = None                       # applied by the GEMM's epilogue
-    else:
-        src, splits = G.workspace(xr.device, p.splits * B * Nn * 4), p.splits
-        if not (isinstance(x, NormedRows)
-                and _gemv_prologue(x, w, "splitk", p, None, Nn, ws=src)):
-            if isinstance(x, NormedRows):
-                x = x.materialize()
-            fmt = _slab_gemm(x, w, p, src)
+    else:           # x a NormedRows: _split_slabs tries the prologue GEMV, then the norm
+        (_, src, fmt), splits = _split_slabs(x, w, p), p.splits
     out = torch.empty(B, hq * hd, dtype=x.dtype, device=x.device)
     bias, q_w, k_w, eps = _qkv_extras(bias, qk_norm, Nn, hd)
     _native_call("dli_decode_attention_fused", _p(out), _p(src), splits, _p(positions),
@@ -1069,15 +1077,9 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     if p_gu.splits == 1 and p_gu.tile in G.GATHER_TILES and x.is_contiguous():
         # the gate/up GEMM reads the token rows in place through the permutation (no gathered
         # copy of them: dli_gemm_grouped_gather, the generic tile family)
-        if tl_gu is not None:
-            _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w_gu),
-                         w_gu.stride(-2), _p(act), act.stride(0), n, F2, D,
-                         G.EPI["silu_mul"], p_gu.tile, 1, _p(src), None, _p(offsets), E_local,
-                         _p(tl_gu[0]), tl_gu[1], _st())
-        else:
-            _native_call("dli_gemm_grouped_gather", _p(x), x.stride(0), _p(w_gu),
-                         w_gu.stride(-2), _p(act), act.stride(0), n, F2, D, p_gu.tile, _p(src),
-                         _p(offsets), E_local, _st())
+        # (on the compact grid: dli_gemm_grouped_list with the same row permutation)
+        _launch_gemm("gemm", x, w_gu, p_gu, G.EPI["silu_mul"], act, act.stride(0), n, F2, D,
+                     group_off=offsets, groups=E_local, tile_list=tl_gu, arow=src)
     else:
         # permuted rows: at most n (all local); rows past offsets[E_local] are never touched
         xp = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
@@ -1114,14 +1116,8 @@ def _moe_down_slabs(act, w_down, offsets, n: int, p: G.GemmPlan, tile_list=None)
     grid (``_gemm_native``)."""
     E_local, D, F = w_down.shape
     ws = G.workspace(act.device, p.splits * max(n, 1) * D * 2)
-    if tile_list is not None:
-        _native_call("dli_gemm_grouped_list", _p(act), act.stride(0), _p(w_down),
-                     w_down.stride(-2), None, D, n, D, F, G.EPI["slab16"], p.tile, p.splits,
-                     None, _p(ws), _p(offsets), E_local, _p(tile_list[0]), tile_list[1], _st())
-    else:
-        _native_call("dli_gemm", _p(act), act.stride(0), _p(w_down), w_down.stride(-2), None,
-                     D, n, D, F, G.EPI["slab16"], p.tile, p.splits, None, _p(ws), _p(offsets),
-                     E_local, _st())
+    _launch_gemm("gemm", act, w_down, p, G.EPI["slab16"], None, D, n, D, F, ws=ws,
+                 group_off=offsets, groups=E_local, tile_list=tile_list)
     return ws
 
 
