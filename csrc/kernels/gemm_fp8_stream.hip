@@ -30,28 +30,35 @@
 // lane reads past the scale tensor (group and block clamped). The launcher refuses what the
 // kernel cannot take: K or ldw not in whole 16-byte chunks, unaligned operands, a split whose
 // slices do not start on a multiple of 128.
+//
+// dli_gemm_fp8_stream_grouped is the same loop (fp8_stream_tile) for an ops.Fp8Experts stack
+// (q [E, N, K], scales [E, N / 16, ceil(K / 128)]) over the permuted rows of a MoE layer, on the
+// compact grid of the align step's tile list: see gemm_fp8_stream_grouped_kernel.
 #include "gemm_common.h"
 
 typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
 
-template <int MB, int RG, int EPI, int DEPTH>
-__global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
-    const u16* __restrict__ A, int lda, const fp8* __restrict__ Wq, int ldw,
-    const float* __restrict__ S, int sld, void* __restrict__ C, int ldc, int M, int N, int K,
-    int k_split_len, const u16* __restrict__ bias, float* __restrict__ ws) {
+// One workgroup's tile: the 16 MB rows xrow(0 .. M) against the weight rows of column block cb,
+// over K slice ks of nks; outputs to rows crow0 + r of C. Shared by the dense grid (the rows of
+// A, crow0 0) and the grouped one (an item of an expert's rows, gemm_fp8_stream_grouped_kernel).
+template <int MB, int RG, int EPI, int DEPTH, class XRow>
+__device__ __forceinline__ void fp8_stream_tile(
+    XRow xrow, const fp8* __restrict__ Wq, int ldw, const float* __restrict__ S, int sld,
+    void* __restrict__ C, int ldc, int crow0, int M, int N, int K, int k_split_len, int cb, int ks,
+    int nks, const u16* __restrict__ bias, float* __restrict__ ws) {
   static_assert(DEPTH % 2 == 0, "block t uses LDS buffer t & 1 = u & 1");
   static_assert(EPI != EPI_SILU || RG <= 2, "a gate/up pair is two groups");
   constexpr int ROWS = 16 * MB;
   constexpr int RS = 17;                        // 16-B vectors per LDS row: 16 + 1 of padding
   __shared__ u32x4s xs[2][ROWS * RS];
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
-  const int ks = blockIdx.y, kb = ks * k_split_len;
+  const int kb = ks * k_split_len;
   const int klen = min(k_split_len, K - kb);
   const int nchunk = klen >> 4;                 // 16-element weight chunks of the slice
   const int nx = klen >> 3;                     // 8-element x vectors of the slice
   const int nblk = (klen + 127) >> 7;           // scale blocks (the last may be partial)
   const int ngrp = N >> 4;
-  const int g0 = ((int)blockIdx.x * 4 + wid) * RG;   // the wave's first scale group
+  const int g0 = (cb * 4 + wid) * RG;           // the wave's first scale group
   const u32x4s* wrow[RG];
   const float* srow[RG];
 #pragma unroll
@@ -65,7 +72,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
   const u32x4s* xsrc[MB];
 #pragma unroll
   for (int j = 0; j < MB; ++j)
-    xsrc[j] = reinterpret_cast<const u32x4s*>(A + (long)min(xr + 16 * j, M - 1) * lda + kb);
+    xsrc[j] = reinterpret_cast<const u32x4s*>(xrow(min(xr + 16 * j, M - 1)) + kb);
 
   u32x4s w[DEPTH][RG][2];
   float sc[DEPTH][RG];
@@ -154,7 +161,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
 #undef DLI_F8S_ISSUE
 
   // epilogue: lane (fr, fq) holds C[16 i + fr][16 (g0 + g) + 4 fq .. +4)
-  if (gridDim.y > 1) {                          // fp32 partial slab of this K slice (format 0)
+  if (nks > 1) {                                // fp32 partial slab of this K slice (format 0)
     float* slab = ws + (long)ks * M * N;
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
@@ -174,7 +181,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
       for (int i = 0; i < MB; ++i) {
         const int row = 16 * i + fr;
         if (row < M && g0 < ngrp)
-          store_silu_quad(C, ldc, row, (g0 >> 1) * 16 + 4 * fq, acc[i][0], acc[i][1], vec);
+          store_silu_quad(C, ldc, crow0 + row, (g0 >> 1) * 16 + 4 * fq, acc[i][0], acc[i][1], vec);
       }
     } else {
       // RG 1: wave 2 p holds the gate group, wave 2 p + 1 its up group, met through LDS
@@ -191,7 +198,7 @@ __global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
           const int row = 16 * i + fr;
           const f32x4 up = ex[((wid >> 1) * MB + i) * 64 + lane];
           if (row < M && g0 < ngrp)
-            store_silu_quad(C, ldc, row, (g0 >> 1) * 16 + 4 * fq, acc[i][0], up, vec);
+            store_silu_quad(C, ldc, crow0 + row, (g0 >> 1) * 16 + 4 * fq, acc[i][0], up, vec);
         }
       }
     }
@@ -203,8 +210,46 @@ __global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
 #pragma unroll
     for (int g = 0; g < RG; ++g)
       if (row < M && g0 + g < ngrp)
-        store_quad<EPI>(C, ldc, row, 16 * (g0 + g) + 4 * fq, N, acc[i][g], bias, vec);
+        store_quad<EPI>(C, ldc, crow0 + row, 16 * (g0 + g) + 4 * fq, N, acc[i][g], bias, vec);
   }
+}
+
+template <int MB, int RG, int EPI, int DEPTH>
+__global__ void __launch_bounds__(256) gemm_fp8_stream_kernel(
+    const u16* __restrict__ A, int lda, const fp8* __restrict__ Wq, int ldw,
+    const float* __restrict__ S, int sld, void* __restrict__ C, int ldc, int M, int N, int K,
+    int k_split_len, const u16* __restrict__ bias, float* __restrict__ ws) {
+  fp8_stream_tile<MB, RG, EPI, DEPTH>([=](int r) { return A + (long)r * lda; }, Wq, ldw, S, sld,
+                                      C, ldc, 0, M, N, K, k_split_len, (int)blockIdx.x,
+                                      (int)blockIdx.y, (int)gridDim.y, bias, ws);
+}
+
+// The grouped (MoE) form on the compact grid: workgroup y takes item y of the tile list that
+// dli_moe_align_tiles wrote for 16 MB-row items (tl[0] items, tl[1] their height, then
+// (expert, first row) pairs), and runs the tile of that expert's weights Wq[e] / S[e] over its
+// rows [m0, m0 + 16 MB) of the permuted rows go[e] .. go[e + 1). x rows are read through arow
+// (the token of each permuted row: the gate/up projection, no gathered copy) or in place;
+// outputs go to the permuted rows, masked to the item's rows of its expert. An item at or past
+// the count, a list of another height or an expert out of range ends the whole workgroup
+// before its first barrier. No split-K.
+template <int MB, int RG, int EPI, int DEPTH>
+__global__ void __launch_bounds__(256) gemm_fp8_stream_grouped_kernel(
+    const u16* __restrict__ A, int lda, const fp8* __restrict__ Wq, int ldw,
+    const float* __restrict__ S, int sld, void* __restrict__ C, int ldc, int N, int K,
+    const int* __restrict__ arow, const int* __restrict__ go, int groups,
+    const int* __restrict__ tl) {
+  const int it = blockIdx.y;
+  if (it >= tl[0] || tl[1] != 16 * MB) return;
+  const int e = tl[2 + 2 * it], m0 = tl[3 + 2 * it];
+  if (e < 0 || e >= groups || m0 < 0) return;
+  const int row0 = go[e] + m0;
+  const int Mv = min(16 * MB, go[e + 1] - row0);        // the item's rows of its expert
+  if (Mv <= 0) return;
+  const fp8* We = Wq + (long)e * N * ldw;
+  const float* Se = S + (long)e * (N >> 4) * sld;
+  fp8_stream_tile<MB, RG, EPI, DEPTH>(
+      [=](int r) { return A + (long)(arow != nullptr ? arow[row0 + r] : row0 + r) * lda; }, We,
+      ldw, Se, sld, C, ldc, row0, Mv, N, K, K, (int)blockIdx.x, 0, 1, nullptr, nullptr);
 }
 
 template <int MB, int RG, int EPI, int DEPTH>
@@ -266,6 +311,64 @@ extern "C" int dli_gemm_fp8_stream(const void* A, int lda, const void* Wq, const
     case EPI_F32: return dispatch_fp8_stream<EPI_F32>(tile_cfg, A, lda, Wq, scales, sld, ldw, C, ldc, M, N, K, splits, bias, ws, st);
     case EPI_SILU: return dispatch_fp8_stream<EPI_SILU>(tile_cfg, A, lda, Wq, scales, sld, ldw, C, ldc, M, N, K, splits, bias, ws, st);
     case EPI_BIAS: return dispatch_fp8_stream<EPI_BIAS>(tile_cfg, A, lda, Wq, scales, sld, ldw, C, ldc, M, N, K, splits, bias, ws, st);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+template <int EPI>
+static int dispatch_fp8_stream_grouped(int tile_cfg, int mb, const void* A, int lda,
+                                       const void* Wq, const void* S, int sld, int ldw, void* C,
+                                       int ldc, int N, int K, const int* arow, const int* go,
+                                       int groups, const int* tl, int tl_max, hipStream_t st) {
+#define DLI_F8G(MB, RG, DEPTH)                                                                \
+  gemm_fp8_stream_grouped_kernel<MB, RG, EPI, DEPTH>                                          \
+      <<<dim3(((N >> 4) + 4 * RG - 1) / (4 * RG), tl_max), 256, 0, st>>>(                     \
+          (const u16*)A, lda, (const fp8*)Wq, ldw, (const float*)S, sld, C, ldc, N, K, arow,  \
+          go, groups, tl)
+#define DLI_F8G_MB(MB)                                                                        \
+  case MB:                                                                                    \
+    if (tile_cfg == 70) DLI_F8G(MB, 1, 4);                                                    \
+    else DLI_F8G(MB, 2, 2);                                                                   \
+    break
+  switch (mb) {
+    DLI_F8G_MB(1);
+    DLI_F8G_MB(2);
+    DLI_F8G_MB(3);
+    DLI_F8G_MB(4);
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef DLI_F8G_MB
+#undef DLI_F8G
+  DLI_RETURN_LAUNCH();
+}
+
+// The grouped FP8 weight stream: Wq [groups, N, ldw] e4m3fn, scales [groups, N / 16, sld] fp32,
+// M the total permuted rows, group_off int[groups + 1] their offsets per expert, tile_list what
+// dli_moe_align_tiles wrote for bm-row items (bm 16 / 32 / 48 / 64) and max_items
+// (>= ceil(M / bm) + groups) the host bound on its count that sizes the grid. arow (nullable):
+// the row of A behind each permuted row. Epilogues bf16, fp32 and SiLU(gate) * up; splits 1.
+extern "C" int dli_gemm_fp8_stream_grouped(const void* A, int lda, const void* Wq,
+                                           const void* scales, int sld, int ldw, void* C, int ldc,
+                                           int M, int N, int K, int epi, int tile_cfg, int splits,
+                                           int bm, const int* arow, const int* group_off,
+                                           int groups, const int* tile_list, int max_items,
+                                           hipStream_t st) {
+  if (tile_cfg != 70 && tile_cfg != 71) return (int)hipErrorInvalidValue;
+  if (splits != 1 || group_off == nullptr || tile_list == nullptr || groups < 1 || bm < 16 ||
+      bm > 64 || bm % 16)
+    return (int)hipErrorInvalidValue;
+  if (M < 0 || max_items > 65535 || (long)max_items < ((long)M + bm - 1) / bm + groups)
+    return (int)hipErrorInvalidValue;
+  if (M == 0 || N <= 0) return 0;
+  if (N % 16 || K < 16 || K % 16 || ldw % 16 || ldw < K || lda % 8 || lda < K || A == nullptr ||
+      Wq == nullptr || scales == nullptr || C == nullptr ||
+      ((uintptr_t)A | (uintptr_t)Wq) % 16 || sld < (K + 127) / 128)
+    return (int)hipErrorInvalidValue;
+  if (epi == EPI_SILU && N % 32) return (int)hipErrorInvalidValue;
+  switch (epi) {
+    case EPI_BF16: return dispatch_fp8_stream_grouped<EPI_BF16>(tile_cfg, bm / 16, A, lda, Wq, scales, sld, ldw, C, ldc, N, K, arow, group_off, groups, tile_list, max_items, st);
+    case EPI_F32: return dispatch_fp8_stream_grouped<EPI_F32>(tile_cfg, bm / 16, A, lda, Wq, scales, sld, ldw, C, ldc, N, K, arow, group_off, groups, tile_list, max_items, st);
+    case EPI_SILU: return dispatch_fp8_stream_grouped<EPI_SILU>(tile_cfg, bm / 16, A, lda, Wq, scales, sld, ldw, C, ldc, N, K, arow, group_off, groups, tile_list, max_items, st);
     default: return (int)hipErrorInvalidValue;
   }
 }

@@ -8,7 +8,8 @@ launcher for an 8-GPU MI355X box.
     serve-worker    [--port 5000] [--gpu i]             one worker bound to one GPU (or CPU)
                     (every serve-* command takes --kv-dtype bf16|fp8: the element type of
                     the paged KV cache, default the environment's KV_CACHE_DTYPE or bf16;
-                    serve-worker / serve-node / serve-pipeline take --weight-dtype bf16|fp8:
+                    serve-worker / serve-node / serve-pipeline / serve-expert take
+                    --weight-dtype bf16|fp8:
                     fp8 = block-scaled FP8 projection weights, default WEIGHT_DTYPE)
     serve-node      --gpus N [--base-port 5000] [--master URL]
                     one worker process per GPU (--gpu i, port base+i; every GPU stays
@@ -200,6 +201,9 @@ def _serve_expert(argv):
                          "reads all attention tensors and only its own experts' rows")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
+                    help="fp8: block-scaled FP8 projection and expert weights (Qwen3-MoE "
+                         "models; default: WEIGHT_DTYPE, or as the checkpoint holds them)")
     a = ap.parse_args(argv)
     from . import launch
     if not launch.under_launcher():
@@ -234,7 +238,7 @@ def _serve_expert_rank(a):
     kw = {} if cuda else {"num_blocks": 512, "dtype": torch.float32}
     eng = ExpertParallelEngine(a.model, dev, max_batch=a.max_batch,
                                max_model_len=a.max_model_len, model_dir=a.model_dir,
-                               kv_dtype=a.kv_dtype, **kw)
+                               kv_dtype=a.kv_dtype, weight_dtype=a.weight_dtype, **kw)
     eng.warmup()
     logging.basicConfig(level=logging.INFO)
     s = get_settings()

@@ -70,17 +70,19 @@ class TransformerLM:
 
     def _layer_params(self, i: int) -> dict:
         """Layer ``i``'s tensors by short name; an FP8 projection and its ``_scale`` tensor
-        (models/weights.py) as one ``ops.Fp8Weight``."""
+        (models/weights.py) as one ``ops.Fp8Weight``, an expert stack's as one
+        ``ops.Fp8Experts``."""
         pre = f"layers.{i}."
         lp = {k[len(pre):]: v for k, v in self.params.items() if k.startswith(pre)}
         for k in [k for k in lp if k + "_scale" in lp]:
-            lp[k] = ops.Fp8Weight(lp[k], lp.pop(k + "_scale"))
+            pair = ops.Fp8Experts if lp[k].dim() == 3 else ops.Fp8Weight
+            lp[k] = pair(lp[k], lp.pop(k + "_scale"))
         return lp
 
     def _bind_layers(self) -> None:
         self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
         fp8 = [w.numel() for lp in self.layers for w in lp.values()
-               if isinstance(w, ops.Fp8Weight)]
+               if isinstance(w, (ops.Fp8Weight, ops.Fp8Experts))]
         if fp8:      # the bf16 scratch of the dequantise-then-GEMM path, before the KV pool
             ops.reserve_fp8_scratch(self.device, max(fp8))
 
@@ -90,8 +92,8 @@ class TransformerLM:
         return "fp8" if W.is_fp8(self.params) else "bf16"
 
     def quantize_fp8(self) -> "TransformerLM":
-        """Quantise the four projections of every (dense llama) layer in place of their bf16
-        tensors (``weights.quantize_params``)."""
+        """Quantise the four projections of every llama-family layer, expert stacks included,
+        in place of their bf16 tensors (``weights.quantize_params``)."""
         self.layers = []             # no second reference keeps a bf16 projection alive
         W.quantize_params(self.cfg, self.params, inplace=True)
         self._bind_layers()

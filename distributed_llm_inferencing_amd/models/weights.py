@@ -6,10 +6,12 @@ llama / mixtral (per layer ``layers.{i}.``):
     attn_norm [D], wqkv [(Hq+2Hkv)*hd, D], wo [D, Hq*hd], mlp_norm [D],
     (qk_norm, Qwen3) q_norm [hd], k_norm [hd]; (qkv_bias, Qwen2) bqkv [(Hq+2Hkv)*hd]
     dense: w_gu [2F, D] (16-row gate/up interleave, see ops/reference.py), w_down [D, F]
-    FP8 weights (dense llama family only): wqkv / wo / w_gu / w_down may be float8_e4m3fn,
+    FP8 weights (llama family): wqkv / wo / w_gu / w_down may be float8_e4m3fn,
     each with a fp32 ``<name>_scale`` [N/16, ceil(K/128)] beside it (ops/reference.py
     ``dequantize_weight``); ``TransformerLM`` pairs the two into an ``ops.Fp8Weight``
     moe:   router [E, D], w_gu [E, 2F, D], w_down [E, D, F]
+    FP8 expert stacks: w_gu / w_down float8_e4m3fn with ``<name>_scale`` [E, N/16, ceil(K/128)]
+    (every expert quantised by itself), paired into an ``ops.Fp8Experts``; the router is bf16
 gpt2 (per layer): ln1_w, ln1_b, wqkv [3D, D], bqkv [3D], wo [D, D], bo [D], ln2_w, ln2_b,
     w_fc [F, D], b_fc [F], w_proj [D, F], b_proj [D]
 globals: embed [V, D], (gpt2) pos_embed [P, D], final_norm [D], (gpt2) final_norm_b [D],
@@ -113,8 +115,13 @@ def random_init(shapes: Dict[str, tuple], device, dtype=torch.bfloat16, seed: in
     return out
 
 
+def _is_expert_tensor(name: str) -> bool:
+    """An expert stack or the FP8 scales that go with it."""
+    return name.endswith((".w_gu", ".w_down", ".w_gu_scale", ".w_down_scale"))
+
+
 def slice_experts(name: str, t: torch.Tensor, expert_range: Optional[tuple]) -> torch.Tensor:
-    if expert_range is None or not (name.endswith(".w_gu") or name.endswith(".w_down")):
+    if expert_range is None or not _is_expert_tensor(name):
         return t
     if t.dim() != 3:
         return t
@@ -160,29 +167,34 @@ def is_fp8(params: Dict[str, torch.Tensor]) -> bool:
     return any(t.dtype == R.FP8_W for t in params.values())
 
 
-def fp8_scratch_bytes(cfg: ModelConfig) -> int:
-    """Bytes of the bf16 scratch a model with FP8 projections reserves: its largest one."""
+def fp8_scratch_bytes(cfg: ModelConfig, experts: Optional[int] = None) -> int:
+    """Bytes of the bf16 scratch a model with FP8 projections reserves: its largest one; for
+    a MoE model the largest expert stack (``experts``: the local experts of an expert-parallel
+    rank, default all), which the dequantise path rewrites whole."""
     d, f = cfg.hidden_size, cfg.intermediate_size
-    return 2 * max(cfg.qkv_size * d, d * cfg.q_size, 2 * f * d, d * f)
+    mlp = 2 * f * d * ((cfg.num_experts if experts is None else experts) if cfg.is_moe else 1)
+    return 2 * max(cfg.qkv_size * d, d * cfg.q_size, mlp)
 
 
 def check_fp8_model(cfg: ModelConfig) -> None:
-    """FP8 weights exist for the dense llama-family layers only."""
+    """FP8 weights exist for the llama-family layers, dense and MoE."""
     if cfg.arch == "gpt2":
         raise ValueError(f"{cfg.name}: weight_dtype fp8 is not available for gpt2 (arch) models")
-    if cfg.is_moe:
-        raise ValueError(f"{cfg.name}: weight_dtype fp8 with num_experts={cfg.num_experts}: the "
-                         "grouped expert GEMMs have no FP8 form")
 
 
 def apply_weight_dtype(model, want: Optional[str]) -> None:
     """Bring a ``TransformerLM`` to the asked weight dtype (``resolve_weight_dtype``): "fp8"
-    quantises a bf16 model's projections (refused for MoE and gpt2); an FP8 checkpoint sets
-    the dtype by itself, and an explicit "bf16" for one is an error, not a silent
-    dequantise."""
+    quantises a bf16 model's projections (refused for gpt2, and among the MoE models for all
+    but Qwen3-MoE: a Mixtral holds FP8 experts only where its parameters come quantised,
+    ``quantize_params``); an FP8 checkpoint sets the dtype by itself, and an explicit "bf16"
+    for one is an error, not a silent dequantise."""
     have = model.weight_dtype
     if want == "fp8":
         check_fp8_model(model.cfg)
+        cfg = model.cfg
+        if cfg.is_moe and not cfg.qk_norm and have != "fp8":
+            raise ValueError(f"{cfg.name}: weight_dtype fp8 with num_experts={cfg.num_experts}: "
+                             "the switch quantises the experts of Qwen3-MoE models only")
         if have != "fp8":
             model.quantize_fp8()
     elif want == "bf16" and have == "fp8":
@@ -210,6 +222,10 @@ def _fuse(parts, names, fuse):
     return q, R.group_scales(rows)
 
 
+def _stack_fp8(qs):
+    return torch.stack([_u8(q) for q in qs]).view(R.FP8_W)
+
+
 def _cat(ts):
     return torch.cat(ts, 0) if len(ts) > 1 else ts[0]
 
@@ -218,11 +234,22 @@ def _interleave(ts):
     return interleave_gate_up(ts[0], ts[1])
 
 
+def _quantize_proj(w: torch.Tensor, leaf: str, name: str):
+    """(q, scale [N/16, KB]) of one 2-D ``w_gu`` (gate and up quantised apart, per 128 x 128
+    block of the unfused tensors) or any other projection."""
+    if leaf == "w_gu":
+        g, u = R.split_gate_up(w.t())            # rows are the interleaved axis
+        parts = [R.quantize_weight(g.t()), R.quantize_weight(u.t())]
+        return _fuse(parts, [name + "[gate]", name + "[up]"], _interleave)
+    return _fuse([R.quantize_weight(w)], [name], _cat)
+
+
 def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor],
                     inplace: bool = False) -> Dict[str, torch.Tensor]:
-    """The four projections of every dense llama layer in ``params`` as FP8 block-scaled
+    """The four projections of every llama-family layer in ``params`` as FP8 block-scaled
     weights (``reference.quantize_weight`` of each unfused tensor: q / k / v, o, gate / up,
-    down); everything else as it is. Returns a new dict, or with ``inplace`` ``params`` itself,
+    down; of a MoE layer every expert's gate / up / down, the router stays bf16); everything
+    else as it is. Returns a new dict, or with ``inplace`` ``params`` itself,
     each bf16 tensor replaced as soon as it is quantised (a caller that holds no other
     reference then never has the bf16 and the FP8 model in memory together)."""
     check_fp8_model(cfg)
@@ -238,15 +265,17 @@ def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor],
                     ("v", (hq + hkv) * hd, (hq + 2 * hkv) * hd)]
             parts = [R.quantize_weight(w[a:b]) for _, a, b in cuts]
             q, s = _fuse(parts, [f"{name}[{n}]" for n, _, _ in cuts], _cat)
+        elif w.dim() == 3:                       # an expert stack: every expert by itself
+            qs = [_quantize_proj(w[e], leaf, f"{name}[{e}]") for e in range(w.shape[0])]
+            q, s = _stack_fp8([a for a, _ in qs]), torch.stack([b for _, b in qs])
+            del qs
         elif leaf == "w_gu":
-            g, u = R.split_gate_up(w.t())        # rows are the interleaved axis
-            parts = [R.quantize_weight(g.t()), R.quantize_weight(u.t())]
-            q, s = _fuse(parts, [name + "[gate]", name + "[up]"], _interleave)
+            q, s = _quantize_proj(w, leaf, name)
         else:
             parts = [R.quantize_weight(w)]
             q, s = _fuse(parts, [name], _cat)
         out[name], out[name + "_scale"] = q, s
-        del w, parts
+        del w
     return out
 
 
@@ -333,6 +362,13 @@ def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
             out[p + "router"] = cv(sd[moe + "gate.weight"])
             gus, downs = [], []
             if moe + "experts.gate_up_proj" in sd:
+                for t in ("gate_up_proj", "down_proj"):
+                    for suf in ("_scale_inv", ".weight_scale_inv"):
+                        if moe + "experts." + t + suf in sd:
+                            raise ValueError(
+                                f"{moe}experts.{t}{suf}: the fused expert layout with FP8 "
+                                "block scales is not supported (FP8 experts are read from the "
+                                "per-expert experts.{e}.{gate,up,down}_proj tensors)")
                 # fused expert tensors (transformers >= 5 MixtralExperts):
                 # gate_up_proj [E, 2F, D] (gate rows then up rows), down_proj [E, D, F]
                 gu = sd[moe + "experts.gate_up_proj"]
@@ -344,14 +380,41 @@ def from_hf_state_dict(cfg: ModelConfig, sd: Dict[str, torch.Tensor],
                 for e in range(cfg.num_experts):
                     ex = f"{moe}experts.{e}."
                     if ex + "w1.weight" in sd:   # original Mixtral naming (w1 gate, w3 up, w2 down)
-                        g, u, dn = sd[ex + "w1.weight"], sd[ex + "w3.weight"], sd[ex + "w2.weight"]
+                        kg, ku, kd = ex + "w1.weight", ex + "w3.weight", ex + "w2.weight"
                     else:
-                        g, u, dn = (sd[ex + "gate_proj.weight"], sd[ex + "up_proj.weight"],
-                                    sd[ex + "down_proj.weight"])
-                    gus.append(interleave_gate_up(g, u))
-                    downs.append(dn)
-            out[p + "w_gu"] = cv(torch.stack(gus))
-            out[p + "w_down"] = cv(torch.stack(downs))
+                        kg, ku, kd = (ex + "gate_proj.weight", ex + "up_proj.weight",
+                                      ex + "down_proj.weight")
+                    # _hf_proj's rule per expert: FP8 iff its weight_scale_inv is there
+                    gus.append(_hf_proj(sd, [kg, ku], "gu", _interleave, lambda t: t.detach()))
+                    downs.append(_hf_proj(sd, [kd], "dn", _cat, lambda t: t.detach()))
+                for stack, leaf in ((gus, "gu"), (downs, "dn")):
+                    quant = [leaf + "_scale" in d for d in stack]
+                    if any(quant) and not all(quant):
+                        e = quant.index(False)
+                        part = "gate_proj" if leaf == "gu" else "down_proj"
+                        raise ValueError(
+                            f"{moe}experts.{e}.{part}.weight: no weight_scale_inv, while other "
+                            f"experts of layer {i} are FP8: a layer's experts must be quantised "
+                            "all or none")
+                if "gu_scale" in gus[0]:
+                    out[p + "w_gu_scale"] = torch.stack([d["gu_scale"] for d in gus])
+                    gus = [_u8(d["gu"]) for d in gus]
+                else:
+                    gus = [d["gu"] for d in gus]
+                if "dn_scale" in downs[0]:
+                    out[p + "w_down_scale"] = torch.stack([d["dn_scale"] for d in downs])
+                    downs = [_u8(d["dn"]) for d in downs]
+                else:
+                    downs = [d["dn"] for d in downs]
+            if (p + "w_gu_scale" in out) != (p + "w_down_scale" in out):
+                bf = "down_proj" if p + "w_gu_scale" in out else "gate_proj"
+                raise ValueError(
+                    f"{moe}experts.0.{bf}.weight: no weight_scale_inv, while the layer's other "
+                    "expert projections are FP8: a layer's experts must be quantised all or "
+                    "none")
+            fp8cv = lambda t: t.contiguous().view(R.FP8_W)  # noqa: E731
+            out[p + "w_gu"] = (fp8cv if p + "w_gu_scale" in out else cv)(torch.stack(gus))
+            out[p + "w_down"] = (fp8cv if p + "w_down_scale" in out else cv)(torch.stack(downs))
         else:
             out.update(_hf_proj(sd, [h + "mlp.gate_proj.weight", h + "mlp.up_proj.weight"],
                                 p + "w_gu", _interleave, cv))

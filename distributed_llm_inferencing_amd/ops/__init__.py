@@ -265,9 +265,88 @@ class Fp8Weight:
                 and G.stream_slices_ok(self.q.shape[1], p.splits))
 
 
+class Fp8Experts:
+    """A stack of weight-only quantised expert projections: ``q`` [E, N, K] ``float8_e4m3fn``
+    and fp32 ``scale`` [E, N / 16, ceil(K / 128)], every expert an ``Fp8Weight`` of its own:
+    W[e, n, k] = float(q[e, n, k]) * scale[e, n // 16, k // 128]
+    (``reference.dequantize_experts``). Looks like its [E, N, K] tensor to ``moe_mlp`` and the
+    planner; a decode step streams it through the grouped FP8 MFMA stream
+    (``dli_gemm_fp8_stream_grouped``) where ``stream_ok`` holds, and every other call runs the
+    bf16 grouped GEMMs on its bf16 image (``bf16()``, the whole stack in one pass)."""
+    __slots__ = ("q", "scale")
+    act_dtype = torch.bfloat16
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dtype != R.FP8_W or q.dim() != 3:
+            raise ValueError(f"Fp8Experts: q must be a 3-D float8_e4m3fn tensor, got {q.dtype} "
+                             f"{tuple(q.shape)}")
+        e, n, k = q.shape
+        if n % R.W_SCALE_ROWS:
+            raise ValueError(f"Fp8Experts: {n} rows, not a multiple of {R.W_SCALE_ROWS}")
+        want = (e, n // R.W_SCALE_ROWS, -(-k // R.W_BLOCK))
+        if scale.dtype != torch.float32 or tuple(scale.shape) != want:
+            raise ValueError(f"Fp8Experts: scale must be fp32 {want} for a stack {(e, n, k)}, "
+                             f"got {scale.dtype} {tuple(scale.shape)}")
+        if scale.device != q.device:
+            raise ValueError("Fp8Experts: q and scale on different devices")
+        self.q, self.scale = q.contiguous(), scale.contiguous()
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    @property
+    def dtype(self):
+        return self.q.dtype
+
+    def dim(self) -> int:
+        return 3
+
+    def numel(self) -> int:
+        return self.q.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def clone(self) -> "Fp8Experts":
+        return Fp8Experts(self.q.clone(), self.scale.clone())
+
+    def to(self, device) -> "Fp8Experts":
+        return Fp8Experts(self.q.to(device), self.scale.to(device))
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        return R.dequantize_experts(self.q, self.scale, dtype)
+
+    def bf16(self) -> torch.Tensor:
+        """The bf16 stack [E, N, K]: on the GPU a view of the per-device scratch of
+        ``Fp8Weight.bf16`` (same validity rule), filled by one ``dli_dequant_fp8_block`` call
+        on the [E * N, K] view (N is a multiple of 16, so no scale group straddles two
+        experts)."""
+        if not self.q.is_cuda:
+            return self.dequantize(torch.bfloat16)
+        e, n, k = self.q.shape
+        reserve_fp8_scratch(self.q.device, e * n * k)
+        out = _fp8_scratch[(self.q.device.type, self.q.device.index)][:e * n * k].view(e, n, k)
+        _native_call("dli_dequant_fp8_block", _p(self.q), _p(self.scale), _p(out), e * n, k,
+                     _st())
+        return out
+
+    def stream_ok(self, rows: int, groups: int, p: G.GemmPlan) -> bool:
+        """Whether the grouped FP8 stream takes ``rows`` permuted rows over ``groups`` experts
+        under ``p``: one of its tiles, unsplit, K in whole 16-element chunks, and a tile list
+        (``G.max_items`` at ``G.fp8_grouped_bm``) that fits one grid dimension."""
+        return (p.tile in G.FP8_STREAM_TILES and p.splits == 1 and rows > 0
+                and groups == self.q.shape[0] and G.stream_slices_ok(self.q.shape[2], 1)
+                and G.max_items(rows, groups, G.fp8_grouped_bm(rows, groups)) <= 65535)
+
+
 def _dense(w):
     """The tensor the bf16 kernels (or, off the GPU, the reference ops) read for ``w``."""
-    if isinstance(w, Fp8Weight):
+    if isinstance(w, (Fp8Weight, Fp8Experts)):
         return w.bf16() if w.q.is_cuda else w.dequantize(torch.float32)
     return w
 
@@ -1020,7 +1099,7 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     generic tile family run on the compact grid over the align step's tile list
     (``G.list_plan``), whose size does not grow as rows x experts."""
     if not _use_native(x):
-        return R.moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset)
+        return R.moe_mlp(x, _dense(w_gu), _dense(w_down), topk_w, topk_ids, expert_offset)
     T, D = x.shape
     k = topk_ids.shape[1]
     E_local, F2, _ = w_gu.shape
@@ -1032,14 +1111,19 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     prefill = (n >= _MOE_PREFILL_ROWS * E_local
                and not torch.cuda.is_current_stream_capturing())
     rows = plan_rows if plan_rows is not None else n
-    p_gu = G.grouped_plan(rows, F2, D, "silu_mul", E_local)
-    p_dn = G.grouped_plan(rows, D, F2 // 2, "none", E_local)
+    # FP8 expert stacks (Fp8Experts): a decode step streams them (dli_gemm_fp8_stream_grouped)
+    # where the plan is a stream tile the call can take; else the bf16 plan below runs on the
+    # stack's bf16 image, dequantised right before its GEMM (one scratch for both stacks)
+    sbm = G.fp8_grouped_bm(rows, E_local)
+    p_gu, st_gu = _expert_plan(w_gu, rows, n, F2, D, "silu_mul", E_local, sbm,
+                               not prefill and _rows_aligned(x) and x.is_contiguous())
+    p_dn, st_dn = _expert_plan(w_down, rows, n, D, F2 // 2, "none", E_local, sbm, not prefill)
     # one tile list per row-tile height that the two projections run on the compact grid
     lists = {}
     if not prefill and n > 0:
-        for p in (p_gu, p_dn):
-            bm = G.TILES[p.tile][0]
-            if G.list_plan(p, E_local) and bm not in lists:
+        for p, st in ((p_gu, st_gu), (p_dn, st_dn)):
+            bm = sbm if st else G.TILES[p.tile][0]
+            if (st or G.list_plan(p, E_local)) and bm not in lists:
                 cap = G.max_items(n, E_local, bm)
                 lists[bm] = (torch.empty(1 + cap, 2, dtype=torch.int32, device=dev), cap)
     if lists:
@@ -1050,8 +1134,11 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     else:
         _native_call("dli_moe_align", _p(offsets), _p(pos), _p(src), _p(topk_ids), n, k,
                      expert_offset, E_local, _st())
-    tl_gu = lists.get(G.TILES[p_gu.tile][0]) if G.list_plan(p_gu, E_local) else None
-    tl_dn = lists.get(G.TILES[p_dn.tile][0]) if G.list_plan(p_dn, E_local) else None
+    tl_gu = tl_dn = None
+    if not st_gu and G.list_plan(p_gu, E_local):
+        tl_gu = lists.get(G.TILES[p_gu.tile][0])
+    if not st_dn and G.list_plan(p_dn, E_local):
+        tl_dn = lists.get(G.TILES[p_dn.tile][0])
     act = torch.empty(max(n, 1), F2 // 2, dtype=x.dtype, device=dev)
     if prefill:
         # prefill-sized expert GEMMs (thousands of rows per expert) are compute-bound: a
@@ -1067,14 +1154,17 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
         y = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
         if rows_max > 0:
             p8 = G.GemmPlan("dli", G.MOE_PREFILL_TILE, 1)
-            _gemm_native(xp, w_gu, "silu_mul", out=act, groups=E_local, group_off=offsets,
-                         rows_per_group=rows_max, plan=p8)
-            _gemm_native(act, w_down, "none", out=y, groups=E_local, group_off=offsets,
+            _gemm_native(xp, _stack(w_gu), "silu_mul", out=act, groups=E_local,
+                         group_off=offsets, rows_per_group=rows_max, plan=p8)
+            _gemm_native(act, _stack(w_down), "none", out=y, groups=E_local, group_off=offsets,
                          rows_per_group=rows_max, plan=p8)
         out = torch.empty_like(x)
         _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
         return out
-    if p_gu.splits == 1 and p_gu.tile in G.GATHER_TILES and x.is_contiguous():
+    if st_gu:                            # token rows read through the permutation, as below
+        grouped_fp8_stream(x, w_gu, p_gu, "silu_mul", act, offsets, n, sbm, lists[sbm], src)
+    elif p_gu.splits == 1 and p_gu.tile in G.GATHER_TILES and x.is_contiguous():
+        w_gu = _stack(w_gu)
         # the gate/up GEMM reads the token rows in place through the permutation (no gathered
         # copy of them: dli_gemm_grouped_gather, the generic tile family)
         # (on the compact grid: dli_gemm_grouped_list with the same row permutation)
@@ -1083,10 +1173,18 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     else:
         # permuted rows: at most n (all local); rows past offsets[E_local] are never touched
         xp = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
-        _native_call("dli_moe_gather", _p(xp), _p(x), _p(src), n, D, _p(offsets[E_local:]),
+        xc = x if x.is_contiguous() else x.contiguous()      # (the gather reads D-strided rows)
+        _native_call("dli_moe_gather", _p(xp), _p(xc), _p(src), n, D, _p(offsets[E_local:]),
                      _st())
-        _gemm_native(xp, w_gu, "silu_mul", out=act, groups=E_local, group_off=offsets,
+        _gemm_native(xp, _stack(w_gu), "silu_mul", out=act, groups=E_local, group_off=offsets,
                      rows_per_group=n, plan=p_gu, tile_list=tl_gu)
+    if st_dn:
+        y = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
+        grouped_fp8_stream(act, w_down, p_dn, "none", y, offsets, n, sbm, lists[sbm])
+        out = torch.empty_like(x)
+        _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
+        return out
+    w_down = _stack(w_down)
     if moe_slab_plan(p_dn):
         if defer_combine:
             # the down projection's slabs; the combine runs with the next layer's add + norm
@@ -1100,6 +1198,49 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
                  rows_per_group=n, plan=p_dn, tile_list=tl_dn)
     out = torch.empty_like(x)
     _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
+    return out
+
+
+def _stack(w):
+    """The [E, N, K] tensor the bf16 grouped GEMMs read for an expert stack."""
+    return w.bf16() if isinstance(w, Fp8Experts) else w
+
+
+def _rows_aligned(x) -> bool:
+    return x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and x.stride(-1) == 1
+
+
+def _expert_plan(w, rows: int, n: int, Nn: int, K: int, epi: str, groups: int, bm: int,
+                 form_ok: bool):
+    """(plan, streams) of one expert projection of ``moe_mlp``: a bf16 stack's grouped plan as
+    ever; an ``Fp8Experts`` stack's plan under the FP8 key, which streams when it is a stream
+    tile that takes the call (``stream_ok``, ``form_ok``: a decode step with aligned rows)
+    and else gives way to a bf16-family plan of the dequantise path, so a stream tile id
+    never reaches ``dli_gemm``."""
+    if not isinstance(w, Fp8Experts):
+        p = G.grouped_plan(rows, Nn, K, epi, groups)
+        if p.tile in G.FP8_STREAM_TILES:
+            raise ValueError(f"GEMM tile {p.tile} streams FP8 block-scaled weights "
+                             f"(ops.Fp8Experts) only, got a {w.dtype} stack")
+        return p, False
+    p = G.grouped_plan(rows, Nn, K, epi, groups, "fp8")
+    if p.tile not in G.FP8_STREAM_TILES:
+        return p, False
+    if (form_ok and n > 0 and w.stream_ok(n, groups, p)
+            and G.max_items(n, groups, bm) <= 65535):
+        return p, True
+    return G.grouped_plan(rows, Nn, K, epi, groups), False
+
+
+def grouped_fp8_stream(x, w: "Fp8Experts", p: G.GemmPlan, epi: str, out, offsets, n: int,
+                       bm: int, tile_list, arow=None):
+    """out[r] = epi(x[arow[r] or r] @ W[e(r)].T) for the ``n`` permuted rows whose experts
+    ``offsets`` delimits, on the grouped FP8 MFMA stream: ``tile_list`` = (list, max items)
+    of the align step for ``bm``-row items. Rows past ``offsets[-1]`` are not written."""
+    E, Nn, K = w.shape
+    _native_call("dli_gemm_fp8_stream_grouped", _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                 w.scale.stride(1), K, _p(out), out.stride(0), n, Nn, K, G.EPI[epi], p.tile,
+                 p.splits, bm, _p(arow), _p(offsets), E, _p(tile_list[0]), tile_list[1], _st())
     return out
 
 

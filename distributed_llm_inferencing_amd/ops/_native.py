@@ -74,6 +74,10 @@ _SIGS = {
     "dli_dequant_fp8_block": [P, P, P, I, I, P],
     # the FP8 weight stream at 4 < M <= 64 (MFMA tiles 70 / 71): dli_gemv_fp8's arguments
     "dli_gemm_fp8_stream": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    # its grouped (MoE) form on the compact grid: ..., K, epi, tile, splits, bm, arow, group_off,
+    # groups, tile_list, max_items, stream
+    "dli_gemm_fp8_stream_grouped": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, I, P, P, I, P, I,
+                                    P],
     "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

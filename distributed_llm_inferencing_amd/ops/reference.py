@@ -132,6 +132,17 @@ def dequantize_weight(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -> 
     return (q.float() * se[:, :k]).to(dtype)
 
 
+def dequantize_experts(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """An expert stack q [E, N, K], s [E, N / 16, ceil(K / 128)]: ``dequantize_weight`` of every
+    expert, W[e, n, k] = float(q[e, n, k]) * s[e, n // 16, k // 128]."""
+    if q.dim() != 3 or s.dim() != 3 or s.shape[0] != q.shape[0]:
+        raise ValueError(f"scales {tuple(s.shape)} do not fit an FP8 expert stack "
+                         f"{tuple(q.shape)}")
+    if q.shape[0] == 0:
+        return torch.empty(q.shape, dtype=dtype, device=q.device)
+    return torch.stack([dequantize_weight(q[e], s[e], dtype) for e in range(q.shape[0])])
+
+
 def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     """[F, K] x2 -> [2F, K] in the 16-row interleaved layout (see module doc)."""
     f, k = gate.shape

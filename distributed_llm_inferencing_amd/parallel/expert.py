@@ -267,7 +267,7 @@ class ExpertParallelEngine:
                  seed: int = 0, num_blocks: Optional[int] = None, dtype=torch.bfloat16,
                  max_prefill_tokens: int = 16384, lookahead: Optional[bool] = None,
                  comm: Optional[str] = None, model_dir: Optional[str] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, weight_dtype: Optional[str] = None):
         from .transport import init_distributed
         dev = torch.device(device)
         self.rank, self.world = init_distributed(device=dev if dev.type == "cuda" else None)
@@ -322,7 +322,8 @@ class ExpertParallelEngine:
                                 max_model_len=max_model_len, num_blocks=num_blocks,
                                 use_graphs=graphs, lm=lm,
                                 max_prefill_tokens=max_prefill_tokens, lookahead=lookahead,
-                                mixed_steps=False, kv_dtype=kv_dtype)
+                                mixed_steps=False, kv_dtype=kv_dtype,
+                                weight_dtype=weight_dtype)
         self.max_batch = max_batch
         self.device = dev
         self.steps = 0
@@ -583,7 +584,7 @@ def load_ep_params(model_dir: str, cfg, expert_range, device, dtype):
         st = SafetensorsFile(str(f))
         try:
             names = st.keys()
-            experts = [n for n in names if n.endswith(".w_gu") or n.endswith(".w_down")]
+            experts = [n for n in names if W._is_expert_tensor(n)]
             rest = [n for n in names if n not in experts]
             out.update(st.load(rest, device=device))
             for n in experts:
@@ -592,7 +593,9 @@ def load_ep_params(model_dir: str, cfg, expert_range, device, dtype):
             st.close()
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)
-    return {k: (v if v.dtype == dtype else v.to(dtype)) for k, v in out.items()}
+    # (FP8 projections and their fp32 scales stay as they are)
+    return {k: (v if v.dtype in (dtype, W.R.FP8_W) or k.endswith("_scale") else v.to(dtype))
+            for k, v in out.items()}
 
 
 def bench_expert_parallel(args, world, rank, make_prompts):

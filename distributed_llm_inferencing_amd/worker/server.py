@@ -675,7 +675,8 @@ def main(argv=None):
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
     ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
-                    help="fp8: quantise the dense llama-family projections to block-scaled FP8 "
+                    help="fp8: quantise the llama-family projections and experts to block-scaled "
+                         "FP8 "
                          "(default: WEIGHT_DTYPE, or the checkpoint's own)")
     ap.add_argument("--server", default="werkzeug", choices=["werkzeug", "uvicorn", "aiohttp"],
                     help="uvicorn: ASGI front (worker/asgi.py: /inference as a coroutine per "
