@@ -51,6 +51,12 @@ def _hipcc() -> str:
 # -inf as the masked-score / running-max sentinel (poison under ninf -> NaNs).
 KERNEL_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
                 "-munsafe-fp-atomics", "-Wno-unused-result"]
+# Per-file additions to KERNEL_FLAGS. gemm_fp8_tiles.hip scales f32x4 block sums
+# (acc += s * raw): built without the packed fp32 VALU forms (v_pk_fma_f32 and kin), so the
+# sums are scalar v_fma_f32 like the MFMA families' epilogues.
+KERNEL_FILE_FLAGS = {
+    "gemm_fp8_tiles.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 RUNTIME_FLAGS = ["-O2", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
                  "-Wno-unused-result"]
 
@@ -89,6 +95,7 @@ def check_scratch(stderr: str, src: str) -> None:
 
 
 def _compile(src: Path, obj: Path, flags, headers) -> Path:
+    flags = [*flags, *KERNEL_FILE_FLAGS.get(src.name, [])]
     stamp = obj.with_suffix(".sha1")
     dig = _digest([src, *headers], flags)
     if obj.exists() and stamp.exists() and stamp.read_text() == dig:
@@ -129,6 +136,8 @@ def _group_sources(kind: str):
 def source_digest(kind: str) -> str:
     """Digest of one library's sources + headers + flags (``kernels`` or ``runtime``)."""
     srcs, hdrs, flags = _group_sources(kind)
+    if kind == "kernels":
+        flags = [*flags, *(f"{n}:{' '.join(f)}" for n, f in sorted(KERNEL_FILE_FLAGS.items()))]
     return _digest([*srcs, *hdrs], flags)
 
 

@@ -185,8 +185,8 @@ class Fp8Weight:
     (``reference.dequantize_weight``). Looks like its [N, K] tensor to the planner (``shape``,
     ``dim()``, ``device``); the linear ops stream it through the FP8 GEMV kernels at
     M <= ``G.GEMV_MAX_M``, through the FP8 MFMA stream tiles up to ``G.FP8_STREAM_MAX_M`` rows
-    where the autotuner pinned one (``stream_ok``), and run every other shape on its bf16
-    image (``bf16()``)."""
+    and the FP8 LDS tiles up to ``G.FP8_TILE_MAX_M`` rows where the autotuner pinned one
+    (``stream_ok``, ``tiles_ok``), and run every other shape on its bf16 image (``bf16()``)."""
     __slots__ = ("q", "scale")
     act_dtype = torch.bfloat16           # what the activations it meets are
 
@@ -263,6 +263,13 @@ class Fp8Weight:
         chunks and, with split-K, every slice a multiple of 128 (``G.stream_slices_ok``)."""
         return (p.tile in G.FP8_STREAM_TILES and G.GEMV_MAX_M < M <= G.FP8_STREAM_MAX_M
                 and G.stream_slices_ok(self.q.shape[1], p.splits))
+
+    def tiles_ok(self, M: int, p: G.GemmPlan) -> bool:
+        """Whether the FP8 LDS tiles (``dli_gemm_fp8_tiles``) take this call: one of their
+        tiles, ``G.FP8_STREAM_MAX_M`` < M <= ``G.FP8_TILE_MAX_M``, K and every K slice in whole
+        128-column scale blocks (``G.tile_slices_ok``)."""
+        return (p.tile in G.FP8_TILE_TABLE and G.FP8_STREAM_MAX_M < M <= G.FP8_TILE_MAX_M
+                and G.tile_slices_ok(self.q.shape[1], p.splits))
 
 
 class Fp8Experts:
@@ -355,38 +362,47 @@ def _inner_contig(w) -> bool:
     return isinstance(w, Fp8Weight) or w.stride(-1) == 1
 
 
-def _stream_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> bool:
-    """Whether ``p`` runs this call on the FP8 MFMA weight stream (``_pick_kernel``'s first
-    question; never ``w.bf16()``). A stream tile forced on a plain tensor is an error; an
-    ``Fp8Weight`` call the kernel cannot take (``stream_ok``, rows not 16-B aligned,
-    ``form_ok`` False: a grouped call or an epilogue it has not) is False."""
-    if p.tile not in G.FP8_STREAM_TILES:
-        return False
+def _fp8_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> Optional[str]:
+    """The FP8 MFMA kernel that runs this call under ``p`` (``_pick_kernel``'s first question;
+    never ``w.bf16()``): "stream" (the weight stream, ``G.FP8_STREAM_TILES``), "fp8_tiles" (the
+    LDS tiles, ``G.FP8_TILE_TABLE``) or None. Such a tile forced on a plain tensor is an
+    error; an ``Fp8Weight`` call the kernel cannot take (``stream_ok`` / ``tiles_ok``, rows not
+    16-B aligned, ``form_ok`` False: a grouped call or an epilogue it has not) is None."""
+    if p.tile in G.FP8_STREAM_TILES:
+        kind = "stream"
+    elif p.tile in G.FP8_TILE_TABLE:
+        kind = "fp8_tiles"
+    else:
+        return None
     if not isinstance(w, Fp8Weight):
         raise ValueError(f"GEMM tile {p.tile} streams FP8 block-scaled weights "
                          f"(ops.Fp8Weight) only, got a {w.dtype} tensor")
-    return (form_ok and w.stream_ok(x.shape[0], p) and x.stride(0) % 8 == 0
-            and x.data_ptr() % 16 == 0)
+    ok = w.stream_ok if kind == "stream" else w.tiles_ok
+    if (form_ok and ok(x.shape[0], p) and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
+        return kind
+    return None
 
 
 def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
                  keep_splits: bool = False):
     """The one choice of a GEMM's native family: (kind, plan, weight) with kind "stream"
-    (``w`` an ``Fp8Weight`` on the MFMA weight stream), "gemv_fp8" (on the FP8 GEMV stream) or
-    "gemm" (``w`` a plain tensor: the bf16 image of an ``Fp8Weight`` neither stream takes,
-    dequantised here, once). A stream plan the call cannot take (a cached plan met another M,
-    an odd K, a grouped call) gives way to a plan of the bf16 families, so its tile id never
-    reaches ``dli_gemm``: the heuristic plan; with ``keep_splits`` (slabs a fused consumer was
-    sized for) the heuristic's tile at ``p``'s split count; ``grouped_tile`` for a grouped
-    call (``groups`` given)."""
+    (``w`` an ``Fp8Weight`` on the MFMA weight stream), "fp8_tiles" (on the FP8 LDS tiles),
+    "gemv_fp8" (on the FP8 GEMV stream) or "gemm" (``w`` a plain tensor: the bf16 image of an
+    ``Fp8Weight`` none of them takes, dequantised here, once). A stream or FP8 tile plan the
+    call cannot take (a cached plan met another M, an odd K, a grouped call) gives way to a
+    plan of the bf16 families, so its tile id never reaches ``dli_gemm``: the heuristic plan;
+    with ``keep_splits`` (slabs a fused consumer was sized for) the heuristic's tile at ``p``'s
+    split count; ``grouped_tile`` for a grouped call (``groups`` given)."""
     fp8 = isinstance(w, Fp8Weight)
-    if not fp8 and p.tile not in G.FP8_STREAM_TILES:
+    fp8_tile = p.tile in G.FP8_STREAM_TILES or p.tile in G.FP8_TILE_TABLE
+    if not fp8 and not fp8_tile:
         return "gemm", p, w
     M, K = x.shape
     fp8_form = groups is None and epi in G.FP8_STREAM_EPIS
-    if _stream_plan(x, w, p, fp8_form):
-        return "stream", p, w
-    if p.tile in G.FP8_STREAM_TILES:
+    kind = _fp8_plan(x, w, p, fp8_form)
+    if kind is not None:
+        return kind, p, w
+    if fp8_tile:
         if groups is not None:
             p = G.GemmPlan("dli", G.grouped_tile(M, groups), 1)
         elif keep_splits:
@@ -396,6 +412,11 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
     elif fp8_form and w.gemv_ok(M, p):
         return "gemv_fp8", p, w
     return "gemm", p, w.bf16()
+
+
+# the entry of each kind with the FP8 argument list (``_launch_gemm``)
+_FP8_ENTRY = {"stream": "dli_gemm_fp8_stream", "fp8_tiles": "dli_gemm_fp8_tiles",
+              "gemv_fp8": "dli_gemv_fp8"}
 
 
 def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: int, Nn: int,
@@ -409,9 +430,9 @@ def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: i
     pbias = None if bias is None else _p(bias)
     poff = None if group_off is None else _p(group_off)
     if kind != "gemm":
-        _native_call("dli_gemm_fp8_stream" if kind == "stream" else "dli_gemv_fp8", _p(x),
-                     x.stride(0), _p(w.q), _p(w.scale), w.scale.stride(0), K, pC, ldc, rows, Nn,
-                     K, code, p.tile, p.splits, pbias, _p(ws), _st())
+        _native_call(_FP8_ENTRY[kind], _p(x), x.stride(0), _p(w.q), _p(w.scale),
+                     w.scale.stride(0), K, pC, ldc, rows, Nn, K, code, p.tile, p.splits, pbias,
+                     _p(ws), _st())
     elif tile_list is not None:
         _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), pC, ldc,
                      rows, Nn, K, code, p.tile, p.splits, _p(arow), _p(ws), poff, groups,
@@ -573,8 +594,8 @@ def _split_slabs(x, w, plan: Optional[G.GemmPlan] = None, ws=None):
     the plan's split-K partial slabs in the workspace (no output tensor: the consumer reduces
     them), or None where the plan (``plan`` if forced, else the "splitk" plan of the shape)
     does not split. The format the consumer must read: 1 = fp16 x 1/16 (the MFMA families'
-    EPI "slab16" store, half the bytes), 0 = fp32 (the GEMV and FP8 stream tiles, the 4-wave
-    family). ``x`` may be a ``NormedRows``: the GEMV with the norm in its prologue where the
+    EPI "slab16" store, half the bytes), 0 = fp32 (the GEMV tiles, the FP8 stream tiles and
+    the FP8 LDS tiles 72 / 73, the 4-wave family). ``x`` may be a ``NormedRows``: the GEMV with the norm in its prologue where the
     plan has one, else the materialised norm. ``ws``: the caller's own slab buffer."""
     normed = isinstance(x, NormedRows)
     rows = x.residual if normed else x

@@ -74,7 +74,9 @@ _SIGS = {
     "dli_dequant_fp8_block": [P, P, P, I, I, P],
     # the FP8 weight stream at 4 < M <= 64 (MFMA tiles 70 / 71): dli_gemv_fp8's arguments
     "dli_gemm_fp8_stream": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
-    # its grouped (MoE) form on the compact grid: ..., K, epi, tile, splits, bm, arow, group_off,
+    # the FP8 LDS tiles at 64 < M <= 512 (MFMA tiles 72 / 73): the same arguments
+    "dli_gemm_fp8_tiles": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    # the stream's grouped (MoE) form on the compact grid: ..., K, epi, tile, splits, bm, arow, group_off,
     # groups, tile_list, max_items, stream
     "dli_gemm_fp8_stream_grouped": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, I, P, P, I, P, I,
                                     P],

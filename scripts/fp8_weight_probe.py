@@ -4,7 +4,8 @@ graph replays over cold weights (a different weight copy per call, together larg
 Infinity Cache, as bench_decode_tiles.py does). Microseconds and weight GB/s (the weight's
 bytes, scales included, over the time), one JSON line each.
 
-    python scripts/fp8_weight_probe.py [--m 1,2,3,4,8,16,32,64] [--shapes qkv,o,gate_up,down]
+    python scripts/fp8_weight_probe.py [--m 1,2,3,4,8,16,32,64,128,256,512]
+                                       [--shapes qkv,o,gate_up,down]
 
 M <= 4: every GEMV plan (tile x split-K) of each (projection, M, weight dtype), the fastest
 reported. Epilogues are the batch-1 chain's: QKV bf16 rows, O and down adding into the residual
@@ -15,6 +16,10 @@ the MFMA weight-stream tiles, split plans with their reduce kernel), one for the
 of the dequantise + bf16-GEMM path on the same FP8 weight ("fp8_dequant": the dequantise
 kernel's time and its bytes are in it; the rate still counts the FP8 bytes) and one for the
 fastest plan of the bf16-weight GEMM ("bf16"). Epilogues: bf16 rows, gate/up with SiLU*up.
+
+64 < M <= 512: the same three paths, with every plan of the FP8 LDS tiles 72 / 73
+(``G.fp8_tile_plans``, ``path`` "fp8_tiles") in the place of the stream plans. These lines also
+carry the MFMA rate (``tflops``: 2 M N K over the time), the other bound of these shapes.
 """
 import argparse
 import json
@@ -46,7 +51,8 @@ def timed(ops, run, iters, n):
 def line(name, N, K, epi, M, path, p, ms, nbytes, copies):
     print(json.dumps({"shape": name, "N": N, "K": K, "epi": epi, "M": M, "weights": path,
                       "tile": p.tile, "splits": p.splits, "us": round(ms * 1e3, 2),
-                      "weight_gbs": round(nbytes / (ms * 1e-3) / 1e9, 1), "copies": copies}),
+                      "weight_gbs": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                      "tflops": round(2 * M * N * K / (ms * 1e-3) / 1e12, 1), "copies": copies}),
           flush=True)
 
 
@@ -61,8 +67,8 @@ def main():
     from distributed_llm_inferencing_amd.ops import reference as R
     dev = torch.device("cuda")
     ms_ = [int(m) for m in a.m.split(",")]
-    if any(m < 1 or m > G.FP8_STREAM_MAX_M for m in ms_):
-        ap.error(f"--m takes values in 1..{G.FP8_STREAM_MAX_M}")
+    if any(m < 1 or m > G.FP8_TILE_MAX_M for m in ms_):
+        ap.error(f"--m takes values in 1..{G.FP8_TILE_MAX_M}")
     for name in a.shapes.split(","):
         N, K, epi = SHAPES[name]
         wb = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
@@ -97,17 +103,19 @@ def main():
 
 
 def mid_batch(ops, G, name, N, K, epi, M, dt, ws_, x, nbytes, iters):
-    """4 < M <= 64 on one weight dtype: see the module docstring."""
+    """4 < M <= 512 on one weight dtype: see the module docstring."""
     def time_plan(p):
         def run():
             for w in ws_:
                 ops._gemm_native(x, w, epi, plan=p)
         return timed(ops, run, iters, len(ws_))
     if dt == "fp8":
-        for p in G.fp8_stream_plans(M, N, K, epi):
-            ms = time_plan(p)
-            if ms is not None:
-                line(name, N, K, epi, M, "fp8_stream", p, ms, nbytes, len(ws_))
+        for path, ps in (("fp8_stream", G.fp8_stream_plans(M, N, K, epi)),
+                         ("fp8_tiles", G.fp8_tile_plans(M, N, K, epi))):
+            for p in ps:
+                ms = time_plan(p)
+                if ms is not None:
+                    line(name, N, K, epi, M, path, p, ms, nbytes, len(ws_))
     best = None
     for p in G.candidate_plans(M, N, K, epi):
         ms = time_plan(p)
