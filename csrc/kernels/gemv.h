@@ -1,7 +1,9 @@
 // Weight-streaming skinny GEMM for M <= 4 rows (tile ids 29-33, 56-59), shared by its two
-// weight element types: bf16 (gemv.hip: dli_gemm's GEMV tiles, dli_gemv_fused) and FP8
-// block-scaled weights (gemv_fp8.hip: dli_gemv_fp8, dli_gemv_fused_fp8).
+// weight element types: bf16 (gemv.hip: dli_gemm's GEMV tiles, dli_gemv_fused), FP8
+// block-scaled weights (gemv_fp8.hip: dli_gemv_fp8, dli_gemv_fused_fp8) and 4-bit group-scaled
+// weights (gemv_w4.hip: dli_gemv_w4, dli_gemv_fused_w4).
 #pragma once
+#include <type_traits>
 #include "gemm_common.h"
 
 // ---------------------------------------------------------------------------------------
@@ -19,6 +21,7 @@
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 
 // bf16 pairs by __builtin_shufflevector: a __builtin_bit_cast of one element of a uint
 // ext-vector was compiled (ROCm 7.2 clang) into the FIRST element for every lane pair
@@ -56,6 +59,27 @@ struct WFp8 {
   static constexpr int SH = 4;
   typedef u32x4v vec;
 };
+// WInt4 (ops/reference.py dequantize_weight_w4): [N, ldw / 2] bytes of nibbles q in 0..15 and
+// sz[N, sld] words (fp16 scale bits | zero point << 16), one per row and 128 K-elements:
+// W[n, k] = (q[n, k] - z[n][k >> 7]) * s[n][k >> 7]. Nibble i of a 32-bit word holds element
+// [0, 2, 4, 6, 1, 3, 5, 7][i] of its 8, so ((word >> 4 i) & 0x000F000F) | 0x43004300 is the
+// bf16 pair (128 + q[2 i], 128 + q[2 i + 1]) (0x4300 is 128.0 with ulp 1: exact). A lane's load
+// is a chunk of 1 << SH K-elements (SH 4: 8 B, two x vectors; SH 5: 16 B, four), which lies in
+// one 128-group; its pairs are dotted against the x pairs as they are and the zero point
+// leaves in fp32: acc += s * (dot(128 + q, x) - (128 + z) * xsum), xsum the chunk's x sum,
+// computed once per (x row, step) for the wave's RW rows. Every row has scales of its own: RW
+// sz words per step, the row and the chunk clamped as the weight loads are.
+template <int SH_>
+struct WInt4 {
+  const uint8_t* p;
+  const uint32_t* sz;
+  int sld;
+  static constexpr int SH = SH_;
+  static_assert(SH_ == 4 || SH_ == 5, "a chunk is an 8-B or a 16-B load");
+  typedef typename std::conditional<SH_ == 5, u32x4v, u32x2v>::type vec;
+};
+template <class WT> struct is_w4 { static constexpr bool value = false; };
+template <int SH_> struct is_w4<WInt4<SH_>> { static constexpr bool value = true; };
 
 // the x values one weight chunk meets: one 16-B vector (bf16 weights) or two (FP8)
 template <class WT> struct XChunk;
@@ -81,6 +105,37 @@ template <> struct XChunk<WFp8> {
   }
 };
 
+template <int SH_> struct XChunk<WInt4<SH_>> {
+  static constexpr int NX = 1 << (SH_ - 3);         // x vectors (and weight words) per chunk
+  bf16x8v x[NX];
+  float xs;
+  __device__ __forceinline__ void load(const bf16x8v* xr, int ci) {
+#pragma unroll
+    for (int j = 0; j < NX; ++j) x[j] = xr[NX * ci + j];
+    const u32x4v one = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
+    xs = 0.f;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) xs = dot8_acc(__builtin_bit_cast(bf16x8v, one), x[j], xs);
+  }
+  // zs: the row's sz word of this chunk's group
+  __device__ __forceinline__ float acc(const typename WInt4<SH_>::vec w, float acc,
+                                       uint32_t zs) const {
+    float d = 0.f;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const uint32_t v = w[j];
+      const u32x4v c = {(v & 0x000F000Fu) | 0x43004300u, ((v >> 4) & 0x000F000Fu) | 0x43004300u,
+                        ((v >> 8) & 0x000F000Fu) | 0x43004300u,
+                        ((v >> 12) & 0x000F000Fu) | 0x43004300u};
+      d = dot8_acc(__builtin_bit_cast(bf16x8v, c), x[j], d);
+    }
+    // 128 + z as fp32: 0x43000000 has ulp 2^-16, so z sits at bit 16, where sz keeps it
+    const float zf = __uint_as_float(0x43000000u | (zs & 0x000F0000u));
+    const float sc = (float)__builtin_bit_cast(_Float16, (uint16_t)(zs & 0xFFFFu));
+    return fmaf(sc, fmaf(-zf, xs, d), acc);
+  }
+};
+
 struct NoPrologue {
   __device__ void issue() {}
   __device__ void complete() {}
@@ -102,7 +157,8 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
                                           int ks, float (&res)[MB][4 * RW], Pro& pro) {
   // r0: this wave's first weight row (rows r0 .. r0 + RW - 1 land in res[.][wid * RW ..])
   typedef typename WT::vec wvec;
-  constexpr bool W8 = WT::SH == 4;
+  constexpr bool W8 = std::is_same<WT, WFp8>::value, W4 = is_w4<WT>::value;
+  constexpr int ZR = W4 ? RW : 1;                   // W4: a (scale, zero) word per row and step
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int kb = ks * k_split_len;
   const int klen = min(k_split_len, K - kb);
@@ -111,7 +167,18 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
 #pragma unroll
   for (int r = 0; r < RW; ++r) {
     const int n = min(r0 + r, N - 1);
-    wrow[r] = reinterpret_cast<const wvec*>(W.p + (long)n * ldw + kb);
+    if constexpr (W4)
+      wrow[r] = reinterpret_cast<const wvec*>(W.p + (((long)n * ldw + kb) >> 1));
+    else
+      wrow[r] = reinterpret_cast<const wvec*>(W.p + (long)n * ldw + kb);
+  }
+  // W4: every row's sz row, and the slice's first chunk in chunks
+  const uint32_t* zrow[ZR];
+  int cb4 = 0;
+  if constexpr (W4) {
+    cb4 = kb >> WT::SH;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) zrow[r] = W.sz + (long)min(r0 + r, N - 1) * W.sld;
   }
   // FP8: the scale row of this wave's 16-row group, and the slice's first chunk in chunks
   const float* srow = nullptr;
@@ -131,6 +198,7 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
     pro.issue();
     wvec w[UNROLL][RW];
     float sc[UNROLL];
+    uint32_t zs[UNROLL][ZR];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
 #pragma unroll
@@ -138,6 +206,11 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
         w[u][r] = __builtin_nontemporal_load(wrow[r] + min(c + 64 * u, nchunk - 1));
       sc[u] = 0.f;
       if constexpr (W8) sc[u] = srow[(cb + min(c + 64 * u, nchunk - 1)) >> 3];
+      if constexpr (W4) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+          zs[u][r] = zrow[r][(cb4 + min(c + 64 * u, nchunk - 1)) >> (7 - WT::SH)];
+      }
     }
     pro.complete();
 #pragma unroll
@@ -151,7 +224,9 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
         xv.load(xrow[m], min(c + 64 * u, nchunk - 1));
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
-          const float a = xv.acc(w[u][r], acc[m][r], sc[u]);
+          float a;
+          if constexpr (W4) a = xv.acc(w[u][r], acc[m][r], zs[u][r]);
+          else a = xv.acc(w[u][r], acc[m][r], sc[u]);
           acc[m][r] = ok ? a : acc[m][r];
         }
       }
@@ -172,12 +247,17 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
   for (; c + 64 * (UNROLL - 1) < nchunk; c += 64 * UNROLL) {
     wvec w[UNROLL][RW];
     float sc[UNROLL];
+    uint32_t zs[UNROLL][ZR];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
 #pragma unroll
       for (int r = 0; r < RW; ++r) w[u][r] = __builtin_nontemporal_load(wrow[r] + c + 64 * u);
       sc[u] = 0.f;
       if constexpr (W8) sc[u] = srow[(cb + c + 64 * u) >> 3];
+      if constexpr (W4) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) zs[u][r] = zrow[r][(cb4 + c + 64 * u) >> (7 - WT::SH)];
+      }
     }
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
@@ -186,13 +266,17 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
         XChunk<WT> xv;
         xv.load(xrow[m], c + 64 * u);
 #pragma unroll
-        for (int r = 0; r < RW; ++r) acc[m][r] = xv.acc(w[u][r], acc[m][r], sc[u]);
+        for (int r = 0; r < RW; ++r) {
+          if constexpr (W4) acc[m][r] = xv.acc(w[u][r], acc[m][r], zs[u][r]);
+          else acc[m][r] = xv.acc(w[u][r], acc[m][r], sc[u]);
+        }
       }
     }
   }
   if (c < nchunk) {
     wvec w[UNROLL][RW];
     float sc[UNROLL];
+    uint32_t zs[UNROLL][ZR];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
 #pragma unroll
@@ -200,6 +284,11 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
         w[u][r] = __builtin_nontemporal_load(wrow[r] + min(c + 64 * u, nchunk - 1));
       sc[u] = 0.f;
       if constexpr (W8) sc[u] = srow[(cb + min(c + 64 * u, nchunk - 1)) >> 3];
+      if constexpr (W4) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+          zs[u][r] = zrow[r][(cb4 + min(c + 64 * u, nchunk - 1)) >> (7 - WT::SH)];
+      }
     }
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
@@ -210,7 +299,9 @@ __device__ __forceinline__ void gemv_core(const u16* __restrict__ A, int lda, co
         xv.load(xrow[m], min(c + 64 * u, nchunk - 1));
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
-          const float a = xv.acc(w[u][r], acc[m][r], sc[u]);
+          float a;
+          if constexpr (W4) a = xv.acc(w[u][r], acc[m][r], zs[u][r]);
+          else a = xv.acc(w[u][r], acc[m][r], sc[u]);
           acc[m][r] = ok ? a : acc[m][r];
         }
       }
@@ -388,7 +479,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(
 // nw != null (PRO): A is the raw residual, normalised per row into LDS by the prologue
 // (MB * K * 2 bytes of dynamic LDS, <= 64 KB). FP8 weights: K, ldw and every K slice in
 // whole 16-element chunks, N in whole 16-row scale groups, a scale row per group that
-// covers K.
+// covers K. W4 weights: K in whole 128-groups, ldw and every K slice in whole chunks, an sz
+// row per weight row that covers K.
 template <int MB, int RW, int EPI, int UNROLL = 2, bool H16 = false, bool PRO = false,
           class WT = WBf16>
 static int launch_gemv(const void* A, int lda, const WT W, int ldw, void* C, int ldc, int M,
@@ -399,8 +491,12 @@ static int launch_gemv(const void* A, int lda, const WT W, int ldw, void* C, int
   if (M > MB || (EPI == EPI_SILU && ((R != 32 && !H16) || N % 32)) || K % CH || lda % 8 ||
       ldw % CH)
     return (int)hipErrorInvalidValue;
-  if constexpr (WT::SH == 4) {
+  if constexpr (std::is_same<WT, WFp8>::value) {
     if (W.s == nullptr || N % 16 || W.sld < (K + 127) / 128) return (int)hipErrorInvalidValue;
+  }
+  if constexpr (is_w4<WT>::value) {
+    if (W.p == nullptr || W.sz == nullptr || K % 128 || W.sld < K / 128)
+      return (int)hipErrorInvalidValue;
   }
   const size_t lds = PRO ? (size_t)MB * K * 2 : 0;
   if (PRO && (nw == nullptr || K > 8192 || lds > 65536)) return (int)hipErrorInvalidValue;

@@ -56,6 +56,8 @@ KERNEL_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gp
 # sums are scalar v_fma_f32 like the MFMA families' epilogues.
 KERNEL_FILE_FLAGS = {
     "gemm_fp8_tiles.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # gemv_w4.hip likewise: acc += s * (dot - (128 + z) * xsum) per row, scalar fp32 FMAs
+    "gemv_w4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 RUNTIME_FLAGS = ["-O2", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
                  "-Wno-unused-result"]

@@ -9,8 +9,9 @@ launcher for an 8-GPU MI355X box.
                     (every serve-* command takes --kv-dtype bf16|fp8: the element type of
                     the paged KV cache, default the environment's KV_CACHE_DTYPE or bf16;
                     serve-worker / serve-node / serve-pipeline / serve-expert take
-                    --weight-dtype bf16|fp8:
-                    fp8 = block-scaled FP8 projection weights, default WEIGHT_DTYPE)
+                    --weight-dtype bf16|fp8|w4:
+                    fp8 = block-scaled FP8 projection weights, w4 = 4-bit group-scaled (AWQ
+                    format) ones, default WEIGHT_DTYPE)
     serve-node      --gpus N [--base-port 5000] [--master URL]
                     one worker process per GPU (--gpu i, port base+i; every GPU stays
                     visible to every worker so a ring formed over them by join-pipeline
@@ -81,9 +82,9 @@ def _serve_node(argv):
     ap.add_argument("--preload", default="")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
-    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
-                    help="fp8: block-scaled FP8 projection weights (default: WEIGHT_DTYPE, or "
-                         "the checkpoint's own)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8", "w4"],
+                    help="fp8: block-scaled FP8 projection weights; w4: 4-bit group-scaled "
+                         "ones (default: WEIGHT_DTYPE, or the checkpoint's own)")
     a = ap.parse_args(argv)
     procs = []
     for i, (cmd, env) in enumerate(node_commands(a.gpus, a.base_port, a.preload, a.kv_dtype,
@@ -127,9 +128,9 @@ def _serve_pipeline(argv):
                     help="DP replica: serve the model as a plain node (no shard rows)")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
-    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
-                    help="fp8: block-scaled FP8 projection weights (default: WEIGHT_DTYPE, or "
-                         "the checkpoint's own)")
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8", "w4"],
+                    help="fp8: block-scaled FP8 projection weights; w4: 4-bit group-scaled "
+                         "ones (default: WEIGHT_DTYPE, or the checkpoint's own)")
     a = ap.parse_args(argv)
     import torch
     from .config import get_settings

@@ -64,13 +64,25 @@ def hf_weight_dtype(c: dict) -> str:
     reads — ``quant_method`` "fp8", e4m3 where a format is stated, ``weight_block_size``
     [128, 128], ``activation_scheme`` "dynamic" or absent (activations are never quantised
     here, so the scheme changes nothing) — ``bf16`` without the block, and an error naming
-    the field for anything else."""
+    the field for anything else. ``w4`` for an AWQ block: ``quant_method`` "awq", ``bits`` 4,
+    ``group_size`` 128, ``zero_point`` true, ``version`` "gemm" (AutoAWQ's GEMM packing) in
+    any letter case."""
     qc = c.get("quantization_config")
     if not qc:
         return "bf16"
+    if qc.get("quant_method") == "awq":
+        for field, want in (("bits", 4), ("group_size", 128), ("zero_point", True)):
+            if qc.get(field) != want or isinstance(qc.get(field), bool) != isinstance(want, bool):
+                raise ValueError(f"quantization_config.{field}={qc.get(field)!r}: AWQ "
+                                 f"checkpoints are read with {field} = {want!r} only")
+        if str(qc.get("version", "")).lower() != "gemm":
+            raise ValueError(f"quantization_config.version={qc.get('version')!r}: only the "
+                             "'gemm' packing of AWQ checkpoints is read")
+        return "w4"
     if qc.get("quant_method") != "fp8":
         raise ValueError(f"quantization_config.quant_method={qc.get('quant_method')!r}: only "
-                         "'fp8' (128 x 128 block-scaled e4m3 weights) is supported")
+                         "'fp8' (128 x 128 block-scaled e4m3 weights) and 'awq' (4 bits, group "
+                         "128, zero points, GEMM packing) are supported")
     fmt = qc.get("fmt", qc.get("format"))
     if fmt is not None and "e4m3" not in str(fmt).lower():
         raise ValueError(f"quantization_config.fmt={fmt!r}: only e4m3 is supported")
@@ -97,7 +109,11 @@ def config_from_hf(c: dict, name: Optional[str] = None,
     result describes a full-attention model, so the context is capped at the window."""
     mt = c.get("model_type", "")
     name = name or c.get("_name_or_path") or mt
-    fp8 = hf_weight_dtype(c) == "fp8"
+    wd = hf_weight_dtype(c)
+    fp8 = wd == "fp8"
+    if wd == "w4" and mt in ("gpt2", "mixtral", "qwen3_moe"):
+        raise ValueError(f"quantization_config (awq) with model_type {mt}: 4-bit weights exist "
+                         "for the dense llama family only (no experts, no gpt2)")
     if fp8 and mt == "gpt2":
         raise ValueError("quantization_config (fp8) with model_type gpt2: FP8 weights exist "
                          "for the llama family only")

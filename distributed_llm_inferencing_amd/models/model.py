@@ -77,25 +77,36 @@ class TransformerLM:
         for k in [k for k in lp if k + "_scale" in lp]:
             pair = ops.Fp8Experts if lp[k].dim() == 3 else ops.Fp8Weight
             lp[k] = pair(lp[k], lp.pop(k + "_scale"))
+        for k in [k for k in lp if k + "_sz" in lp]:      # 4-bit: packed nibbles + sz words
+            lp[k] = ops.W4Weight(lp[k], lp.pop(k + "_sz"))
         return lp
 
     def _bind_layers(self) -> None:
         self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
         fp8 = [w.numel() for lp in self.layers for w in lp.values()
-               if isinstance(w, (ops.Fp8Weight, ops.Fp8Experts))]
+               if isinstance(w, (ops.Fp8Weight, ops.Fp8Experts, ops.W4Weight))]
         if fp8:      # the bf16 scratch of the dequantise-then-GEMM path, before the KV pool
             ops.reserve_fp8_scratch(self.device, max(fp8))
 
     @property
     def weight_dtype(self) -> str:
-        """"fp8" when any projection of this stage is an FP8 block-scaled weight."""
-        return "fp8" if W.is_fp8(self.params) else "bf16"
+        """"fp8" when any projection of this stage is an FP8 block-scaled weight, "w4" when
+        any is a 4-bit group-scaled one."""
+        return W.params_weight_dtype(self.params)
 
     def quantize_fp8(self) -> "TransformerLM":
         """Quantise the four projections of every llama-family layer, expert stacks included,
         in place of their bf16 tensors (``weights.quantize_params``)."""
         self.layers = []             # no second reference keeps a bf16 projection alive
         W.quantize_params(self.cfg, self.params, inplace=True)
+        self._bind_layers()
+        return self
+
+    def quantize_w4(self) -> "TransformerLM":
+        """Quantise the four projections of every dense llama-family layer to 4-bit
+        group-scaled weights in place of their bf16 tensors (``weights.quantize_params``)."""
+        self.layers = []
+        W.quantize_params(self.cfg, self.params, inplace=True, weight_dtype="w4")
         self._bind_layers()
         return self
 

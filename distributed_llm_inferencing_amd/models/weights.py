@@ -9,6 +9,9 @@ llama / mixtral (per layer ``layers.{i}.``):
     FP8 weights (llama family): wqkv / wo / w_gu / w_down may be float8_e4m3fn,
     each with a fp32 ``<name>_scale`` [N/16, ceil(K/128)] beside it (ops/reference.py
     ``dequantize_weight``); ``TransformerLM`` pairs the two into an ``ops.Fp8Weight``
+    4-bit weights (dense llama family): the same four as uint8 [N, K/2] packed nibbles, each
+    with an int32 ``<name>_sz`` [N, K/128] beside it (fp16 scale | zero point << 16,
+    ops/reference.py ``dequantize_weight_w4``), paired into an ``ops.W4Weight``
     moe:   router [E, D], w_gu [E, 2F, D], w_down [E, D, F]
     FP8 expert stacks: w_gu / w_down float8_e4m3fn with ``<name>_scale`` [E, N/16, ceil(K/128)]
     (every expert quantised by itself), paired into an ``ops.Fp8Experts``; the router is bf16
@@ -145,12 +148,12 @@ def nbytes(params: Dict[str, torch.Tensor]) -> int:
 
 
 # ----------------------------------------------------------------------------- FP8 weights
-WEIGHT_DTYPES = ("bf16", "fp8")
+WEIGHT_DTYPES = ("bf16", "fp8", "w4")
 FP8_PROJECTIONS = ("wqkv", "wo", "w_gu", "w_down")
 
 
 def resolve_weight_dtype(weight_dtype: Optional[str] = None) -> Optional[str]:
-    """``"bf16"`` | ``"fp8"`` from the argument or, without one, the environment variable
+    """``"bf16"`` | ``"fp8"`` | ``"w4"`` from the argument or, without one, the environment variable
     ``WEIGHT_DTYPE``; None when neither names one (the weights stay as they come). Anything
     else is an error."""
     import os
@@ -167,8 +170,17 @@ def is_fp8(params: Dict[str, torch.Tensor]) -> bool:
     return any(t.dtype == R.FP8_W for t in params.values())
 
 
+def is_w4(params: Dict[str, torch.Tensor]) -> bool:
+    return any(k.endswith("_sz") for k in params)
+
+
+def params_weight_dtype(params: Dict[str, torch.Tensor]) -> str:
+    """"fp8" / "w4" when any projection in ``params`` is quantised that way, else "bf16"."""
+    return "fp8" if is_fp8(params) else "w4" if is_w4(params) else "bf16"
+
+
 def fp8_scratch_bytes(cfg: ModelConfig, experts: Optional[int] = None) -> int:
-    """Bytes of the bf16 scratch a model with FP8 projections reserves: its largest one; for
+    """Bytes of the bf16 scratch a model with FP8 or 4-bit projections reserves: its largest one; for
     a MoE model the largest expert stack (``experts``: the local experts of an expert-parallel
     rank, default all), which the dequantise path rewrites whole."""
     d, f = cfg.hidden_size, cfg.intermediate_size
@@ -182,14 +194,33 @@ def check_fp8_model(cfg: ModelConfig) -> None:
         raise ValueError(f"{cfg.name}: weight_dtype fp8 is not available for gpt2 (arch) models")
 
 
+def check_w4_model(cfg: ModelConfig) -> None:
+    """4-bit weights exist for the dense llama-family layers: no experts, no gpt2."""
+    if cfg.arch == "gpt2":
+        raise ValueError(f"{cfg.name}: weight_dtype w4 is not available for gpt2 (arch) models")
+    if cfg.is_moe:
+        raise ValueError(f"{cfg.name}: weight_dtype w4 with num_experts={cfg.num_experts}: "
+                         "there are no 4-bit expert kernels")
+
+
 def apply_weight_dtype(model, want: Optional[str]) -> None:
     """Bring a ``TransformerLM`` to the asked weight dtype (``resolve_weight_dtype``): "fp8"
     quantises a bf16 model's projections (refused for gpt2, and among the MoE models for all
     but Qwen3-MoE: a Mixtral holds FP8 experts only where its parameters come quantised,
     ``quantize_params``); an FP8 checkpoint sets the dtype by itself, and an explicit "bf16"
-    for one is an error, not a silent dequantise."""
+    for one is an error, not a silent dequantise. "w4" quantises a bf16 dense llama-family
+    model to 4-bit group-scaled weights (``quantize_params``); a 4-bit (AWQ) checkpoint sets
+    the dtype by itself, and neither quantised format is converted into the other."""
     have = model.weight_dtype
-    if want == "fp8":
+    if want is not None and want != have and have != "bf16" and "w4" in (want, have):
+        raise ValueError(f"{model.cfg.name}: weight_dtype {want} was asked for, but the loaded "
+                         f"weights are {have} (quantised projections with scales); they are "
+                         "not converted silently")
+    if want == "w4":
+        check_w4_model(model.cfg)
+        if have != "w4":
+            model.quantize_w4()
+    elif want == "fp8":
         check_fp8_model(model.cfg)
         cfg = model.cfg
         if cfg.is_moe and not cfg.qk_norm and have != "fp8":
@@ -244,21 +275,46 @@ def _quantize_proj(w: torch.Tensor, leaf: str, name: str):
     return _fuse([R.quantize_weight(w)], [name], _cat)
 
 
-def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor],
-                    inplace: bool = False) -> Dict[str, torch.Tensor]:
+def _quantize_params_w4(cfg: ModelConfig, params, out) -> None:
+    """``quantize_params`` for "w4": per-row scales, so every fused projection is quantised as
+    it stands (``reference.quantize_weight_w4`` -> ``pack_w4``)."""
+    check_w4_model(cfg)
+    for name in [k for k in params if k.rsplit(".", 1)[-1] in FP8_PROJECTIONS]:
+        w = params[name]
+        if name + "_sz" in params:
+            continue
+        if w.dtype == R.FP8_W:
+            raise ValueError(f"{name}: an FP8 projection is not requantised to 4 bits")
+        out[name], out[name + "_sz"] = R.pack_w4(*R.quantize_weight_w4(w, name), name)
+        del w
+
+
+def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor], inplace: bool = False,
+                    weight_dtype: str = "fp8") -> Dict[str, torch.Tensor]:
     """The four projections of every llama-family layer in ``params`` as FP8 block-scaled
     weights (``reference.quantize_weight`` of each unfused tensor: q / k / v, o, gate / up,
     down; of a MoE layer every expert's gate / up / down, the router stays bf16); everything
     else as it is. Returns a new dict, or with ``inplace`` ``params`` itself,
     each bf16 tensor replaced as soon as it is quantised (a caller that holds no other
-    reference then never has the bf16 and the FP8 model in memory together)."""
-    check_fp8_model(cfg)
+    reference then never has the bf16 and the FP8 model in memory together).
+    ``weight_dtype`` "w4" (also accepted in ``inplace``'s position): the same four projections
+    of the dense layers as 4-bit group-scaled weights, ``<name>`` uint8 + ``<name>_sz``."""
+    if isinstance(inplace, str):
+        inplace, weight_dtype = False, inplace
+    if weight_dtype not in ("fp8", "w4"):
+        raise ValueError(f"quantize_params: weight_dtype {weight_dtype!r}, expected fp8 or w4")
     out = params if inplace else dict(params)
+    if weight_dtype == "w4":
+        _quantize_params_w4(cfg, params, out)
+        return out
+    check_fp8_model(cfg)
     hq, hkv, hd = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim
     for name in [k for k in params if k.rsplit(".", 1)[-1] in FP8_PROJECTIONS]:
         w = params[name]
         if w.dtype == R.FP8_W:
             continue
+        if name + "_sz" in params:
+            raise ValueError(f"{name}: a 4-bit projection is not requantised to FP8")
         leaf = name.rsplit(".", 1)[-1]
         if leaf == "wqkv":
             cuts = [("q", 0, hq * hd), ("k", hq * hd, (hq + hkv) * hd),
@@ -280,10 +336,52 @@ def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor],
 
 
 # ----------------------------------------------------------------------------- HF conversion
+def _awq_unpack(t: torch.Tensor) -> torch.Tensor:
+    """AutoAWQ's GEMM packing along the last axis: int32 [R, C] -> integers [R, 8 C], nibble i
+    of word c being column 8 c + W4_ORDER[i]."""
+    nib = (t.to(torch.int32).unsqueeze(-1) >> (torch.arange(8, dtype=torch.int32) * 4)) & 15
+    out = torch.empty_like(nib)
+    out[..., list(R.W4_ORDER)] = nib
+    return out.reshape(t.shape[0], -1).to(torch.uint8)
+
+
+def _hf_proj_awq(sd, bases, name: str, fuse):
+    """One (possibly fused) projection of an AWQ checkpoint from the modules ``bases``
+    (``<base>qweight`` int32 [K, N/8], ``<base>qzeros`` int32 [K/128, N/8], ``<base>scales``
+    fp16 [K/128, N]): unpacked to [N, K] integers with [N, K/128] scales and zero points, fused
+    by rows, packed along K: {name: uint8 [N, K/2], name_sz: int32 [N, K/128]}."""
+    qs, ss, zs = [], [], []
+    for b in bases:
+        qw, qz, sc = sd[b + "qweight"], sd[b + "qzeros"], sd[b + "scales"]
+        k, n = qw.shape[0], qw.shape[1] * 8
+        if k % R.W4_GROUP:
+            raise ValueError(f"{b}qweight: K = {k} is not a multiple of the group size "
+                             f"{R.W4_GROUP}")
+        g = k // R.W4_GROUP
+        if qw.dtype != torch.int32 or qz.dtype != torch.int32 or sc.dtype != torch.float16 \
+                or tuple(qz.shape) != (g, n // 8) or tuple(sc.shape) != (g, n):
+            raise ValueError(f"{b}qweight {tuple(qw.shape)} {qw.dtype}: expected qzeros int32 "
+                             f"{(g, n // 8)} and scales fp16 {(g, n)}, got {tuple(qz.shape)} "
+                             f"{qz.dtype} and {tuple(sc.shape)} {sc.dtype}")
+        qs.append(_awq_unpack(qw.detach()).t())
+        zs.append(_awq_unpack(qz.detach()).t())
+        ss.append(sc.detach().t())
+    q, sz = R.pack_w4(fuse(qs).contiguous(), fuse(ss).contiguous(), fuse(zs).contiguous(), name)
+    return {name: q, name + "_sz": sz}
+
+
 def _hf_proj(sd, keys, name: str, fuse, cv):
     """One (possibly fused) projection from the HF tensors ``keys``: {name: bf16 weight}, or,
     when the checkpoint holds ``<key>_scale_inv`` for them (an FP8 block-quantised module;
-    modules it left unconverted have none), {name: e4m3fn weight, name_scale: fp32 scales}."""
+    modules it left unconverted have none), {name: e4m3fn weight, name_scale: fp32 scales}.
+    An AWQ module holds ``qweight`` in place of ``weight`` (``_hf_proj_awq``)."""
+    bases = [k[:-len("weight")] for k in keys]
+    awq = [b + "qweight" in sd for b in bases]
+    if any(awq):
+        if not all(awq):
+            raise ValueError(f"{name}: {[k for k, h in zip(keys, awq) if not h]} are not "
+                             "quantised while the tensors fused with them hold a qweight")
+        return _hf_proj_awq(sd, bases, name, fuse)
     has = [k + "_scale_inv" in sd for k in keys]
     if not any(has):
         return {name: cv(fuse([sd[k] for k in keys]))}

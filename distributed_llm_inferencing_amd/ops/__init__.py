@@ -272,6 +272,87 @@ class Fp8Weight:
                 and G.tile_slices_ok(self.q.shape[1], p.splits))
 
 
+class W4Weight:
+    """A 4-bit group-scaled projection (the AWQ format): ``q_packed`` uint8 [N, K / 2] and
+    ``sz`` int32 [N, K / 128], W[n, k] = (q[n, k] - z[n, k // 128]) * s[n, k // 128]
+    (``reference.dequantize_weight_w4``, which also defines the nibble order and the sz word).
+    Looks like its [N, K] tensor to the planner; the linear ops stream it through the W4 GEMV
+    kernels at M <= ``G.GEMV_MAX_M`` (``gemv_ok``) and run every other shape on its bf16 image
+    (``bf16()``: one dequantise pass into the scratch ``Fp8Weight.bf16`` uses, per call)."""
+    __slots__ = ("q_packed", "sz")
+    act_dtype = torch.bfloat16
+    wdt = "w4"                           # the weight-dtype part of a plan key (``G.wdt``)
+
+    def __init__(self, q_packed: torch.Tensor, sz: torch.Tensor):
+        if q_packed.dtype != torch.uint8 or q_packed.dim() != 2:
+            raise ValueError(f"W4Weight: q_packed must be a 2-D uint8 tensor, got "
+                             f"{q_packed.dtype} {tuple(q_packed.shape)}")
+        n, k = q_packed.shape[0], q_packed.shape[1] * 2
+        if k % R.W4_GROUP:
+            raise ValueError(f"W4Weight: K = {k} is not a multiple of {R.W4_GROUP}")
+        want = (n, k // R.W4_GROUP)
+        if sz.dtype != torch.int32 or tuple(sz.shape) != want:
+            raise ValueError(f"W4Weight: sz must be int32 {want} for a weight {(n, k)}, got "
+                             f"{sz.dtype} {tuple(sz.shape)}")
+        if sz.device != q_packed.device:
+            raise ValueError("W4Weight: q_packed and sz on different devices")
+        self.q_packed, self.sz = q_packed.contiguous(), sz.contiguous()
+
+    @property
+    def shape(self):
+        return torch.Size((self.q_packed.shape[0], self.q_packed.shape[1] * 2))
+
+    @property
+    def device(self):
+        return self.q_packed.device
+
+    @property
+    def dtype(self):
+        return self.q_packed.dtype
+
+    def dim(self) -> int:
+        return 2
+
+    def numel(self) -> int:
+        return self.q_packed.numel() * 2
+
+    def element_size(self) -> float:
+        return 0.5
+
+    def clone(self) -> "W4Weight":
+        return W4Weight(self.q_packed.clone(), self.sz.clone())
+
+    def to(self, device) -> "W4Weight":
+        return W4Weight(self.q_packed.to(device), self.sz.to(device))
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        return R.dequantize_weight_w4(self.q_packed, self.sz, dtype)
+
+    def bf16(self) -> torch.Tensor:
+        """The bf16 weight ``reference.dequantize_weight_w4(q_packed, sz, torch.bfloat16)``: on
+        the GPU a view of the per-device scratch filled by ``dli_dequant_w4`` on the current
+        stream (``Fp8Weight.bf16``'s validity rule)."""
+        if not self.q_packed.is_cuda:
+            return self.dequantize(torch.bfloat16)
+        n, k = self.shape
+        dev = self.q_packed.device
+        reserve_fp8_scratch(dev, n * k)
+        out = _fp8_scratch[(dev.type, dev.index)][:n * k].view(n, k)
+        _native_call("dli_dequant_w4", _p(self.q_packed), _p(self.sz), _p(out), n, k, _st())
+        return out
+
+    def gemv_ok(self, M: int, p: G.GemmPlan) -> bool:
+        """Whether the W4 weight stream takes this call: a GEMV tile, and K and every K slice
+        in whole ``G.W4_CHUNK``-element chunks (K is a multiple of 128 by construction)."""
+        K = self.shape[1]
+        return (M <= G.GEMV_MAX_M and p.tile in G.GEMV_TILES and K % p.splits == 0
+                and (K // p.splits) % G.W4_CHUNK == 0)
+
+
+# the quantised 2-D projections: a stream of their own at M <= 4, ``bf16()`` for the rest
+_QUANT = (Fp8Weight, W4Weight)
+
+
 class Fp8Experts:
     """A stack of weight-only quantised expert projections: ``q`` [E, N, K] ``float8_e4m3fn``
     and fp32 ``scale`` [E, N / 16, ceil(K / 128)], every expert an ``Fp8Weight`` of its own:
@@ -353,13 +434,13 @@ class Fp8Experts:
 
 def _dense(w):
     """The tensor the bf16 kernels (or, off the GPU, the reference ops) read for ``w``."""
-    if isinstance(w, (Fp8Weight, Fp8Experts)):
-        return w.bf16() if w.q.is_cuda else w.dequantize(torch.float32)
+    if isinstance(w, (Fp8Weight, Fp8Experts, W4Weight)):
+        return w.bf16() if w.device.type == "cuda" else w.dequantize(torch.float32)
     return w
 
 
 def _inner_contig(w) -> bool:
-    return isinstance(w, Fp8Weight) or w.stride(-1) == 1
+    return isinstance(w, _QUANT) or w.stride(-1) == 1
 
 
 def _fp8_plan(x, w, p: G.GemmPlan, form_ok: bool = True) -> Optional[str]:
@@ -387,19 +468,21 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
                  keep_splits: bool = False):
     """The one choice of a GEMM's native family: (kind, plan, weight) with kind "stream"
     (``w`` an ``Fp8Weight`` on the MFMA weight stream), "fp8_tiles" (on the FP8 LDS tiles),
-    "gemv_fp8" (on the FP8 GEMV stream) or "gemm" (``w`` a plain tensor: the bf16 image of an
-    ``Fp8Weight`` none of them takes, dequantised here, once). A stream or FP8 tile plan the
+    "gemv_fp8" (on the FP8 GEMV stream), "gemv_w4" (``w`` a ``W4Weight`` on the W4 GEMV stream)
+    or "gemm" (``w`` a plain tensor: the bf16 image of an ``Fp8Weight`` / ``W4Weight`` none of
+    them takes, dequantised here, once). A stream or FP8 tile plan the
     call cannot take (a cached plan met another M, an odd K, a grouped call) gives way to a
     plan of the bf16 families, so its tile id never reaches ``dli_gemm``: the heuristic plan;
     with ``keep_splits`` (slabs a fused consumer was sized for) the heuristic's tile at ``p``'s
     split count; ``grouped_tile`` for a grouped call (``groups`` given)."""
     fp8 = isinstance(w, Fp8Weight)
+    w4 = isinstance(w, W4Weight)
     fp8_tile = p.tile in G.FP8_STREAM_TILES or p.tile in G.FP8_TILE_TABLE
-    if not fp8 and not fp8_tile:
+    if not fp8 and not w4 and not fp8_tile:
         return "gemm", p, w
     M, K = x.shape
     fp8_form = groups is None and epi in G.FP8_STREAM_EPIS
-    kind = _fp8_plan(x, w, p, fp8_form)
+    kind = None if w4 else _fp8_plan(x, w, p, fp8_form)     # (a W4Weight has no MFMA stream)
     if kind is not None:
         return kind, p, w
     if fp8_tile:
@@ -410,13 +493,21 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
         else:
             p = G._heuristic(M, w.shape[-2], K, epi)
     elif fp8_form and w.gemv_ok(M, p):
-        return "gemv_fp8", p, w
+        return ("gemv_w4" if w4 else "gemv_fp8"), p, w
     return "gemm", p, w.bf16()
 
 
 # the entry of each kind with the FP8 argument list (``_launch_gemm``)
 _FP8_ENTRY = {"stream": "dli_gemm_fp8_stream", "fp8_tiles": "dli_gemm_fp8_tiles",
-              "gemv_fp8": "dli_gemv_fp8"}
+              "gemv_fp8": "dli_gemv_fp8", "gemv_w4": "dli_gemv_w4"}
+
+
+def _wq_args(w):
+    """(weight pointer, scale pointer, scale row stride) of a quantised projection, the three
+    arguments its entries take where the bf16 ones take (weight pointer, row stride)."""
+    if isinstance(w, W4Weight):
+        return _p(w.q_packed), _p(w.sz), w.sz.stride(0)
+    return _p(w.q), _p(w.scale), w.scale.stride(0)
 
 
 def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: int, Nn: int,
@@ -430,9 +521,8 @@ def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: i
     pbias = None if bias is None else _p(bias)
     poff = None if group_off is None else _p(group_off)
     if kind != "gemm":
-        _native_call(_FP8_ENTRY[kind], _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                     w.scale.stride(0), K, pC, ldc, rows, Nn, K, code, p.tile, p.splits, pbias,
-                     _p(ws), _st())
+        _native_call(_FP8_ENTRY[kind], _p(x), x.stride(0), *_wq_args(w), K, pC, ldc, rows, Nn,
+                     K, code, p.tile, p.splits, pbias, _p(ws), _st())
     elif tile_list is not None:
         _native_call("dli_gemm_grouped_list", _p(x), x.stride(0), _p(w), w.stride(-2), pC, ldc,
                      rows, Nn, K, code, p.tile, p.splits, _p(arow), _p(ws), poff, groups,
@@ -447,12 +537,15 @@ def _launch_gemm(kind: str, x, w, p: G.GemmPlan, code: int, C, ldc: int, rows: i
 
 def _launch_gemv_fused(rows, norm_w, eps: float, w, C, ldc: int, code: int, tile: int,
                        splits: int, ws):
-    """Marshal the fused GEMV of either weight format: C = epilogue ``code`` of
+    """Marshal the fused GEMV of any weight format: C = epilogue ``code`` of
     (rmsnorm(rows) * norm_w, or ``rows`` as they are when ``norm_w`` is None) @ w.T."""
     M, K = rows.shape
-    fp8 = isinstance(w, Fp8Weight)
-    wargs = (_p(w.q), _p(w.scale), w.scale.stride(0), K) if fp8 else (_p(w), w.stride(-2))
-    _native_call("dli_gemv_fused_fp8" if fp8 else "dli_gemv_fused", _p(rows), rows.stride(0),
+    if isinstance(w, _QUANT):
+        entry = "dli_gemv_fused_w4" if isinstance(w, W4Weight) else "dli_gemv_fused_fp8"
+        wargs = (*_wq_args(w), K)
+    else:
+        entry, wargs = "dli_gemv_fused", (_p(w), w.stride(-2))
+    _native_call(entry, _p(rows), rows.stride(0),
                  _p(norm_w), eps, *wargs, _p(C), ldc, M, w.shape[0], K, code, tile, splits,
                  _p(ws), _st())
 
@@ -477,7 +570,11 @@ def _gemv_prologue(x: NormedRows, w, epi: str, plan: Optional[G.GemmPlan], C, ld
     tiles = G.GEMV_PRO_TILES.get(epi, ())
     if p.tile not in tiles or (p.tile in G.GEMV_PRO_M1_ONLY and M > 1) or M > G.GEMV_MAX_M:
         return False
-    if isinstance(w, Fp8Weight) and not w.gemv_ok(M, p):
+    if isinstance(w, _QUANT) and not w.gemv_ok(M, p):
+        return False
+    if isinstance(w, W4Weight) and p.tile == 31 and M > 2:
+        # the one W4 instantiation below 2 waves per SIMD (4 x rows, 8 weight rows a wave and
+        # the prologue: 256 VGPRs + 8 AGPRs): the norm is materialised and the plain tile runs
         return False
     r = x.residual
     if ws is None and p.splits > 1:      # split K into C: slabs + the reduce kernel
@@ -506,7 +603,7 @@ def linear_residual(x, w, residual, plan: Optional[G.GemmPlan] = None):
     p = plan or G.plan(M, w.shape[0], K, "res", G.wdt(w))
     if (not _use_native(x) or p.tile not in G.GEMV_RES_TILES or M > G.GEMV_MAX_M
             or not residual.is_contiguous() or x.stride(-1) != 1 or not _inner_contig(w)
-            or (isinstance(w, Fp8Weight) and not w.gemv_ok(M, p))):
+            or (isinstance(w, _QUANT) and not w.gemv_ok(M, p))):
         linear_add_rmsnorm(x, w, residual, None, 0.0)
         return
     _launch_gemv_fused(x, None, 0.0, w, residual, residual.stride(0), G.EPI_RES, p.tile, 1,
@@ -534,9 +631,14 @@ def _gemm_native(x, w, epi: str, bias=None, out=None, plan: Optional[G.GemmPlan]
     M, K = x.shape
     Nn = w.shape[-2]
     grouped = group_off is not None
+    forced = plan is not None
     if plan is None:
         plan = (G.grouped_plan(M, Nn, K, epi, groups) if grouped
                 else G.plan(M, Nn, K, epi, G.wdt(w)))
+    if forced and isinstance(w, W4Weight) and (plan.tile in G.FP8_STREAM_TILES
+                                               or plan.tile in G.FP8_TILE_TABLE):
+        raise ValueError(f"GEMM tile {plan.tile} streams FP8 block-scaled weights "
+                         f"(ops.Fp8Weight) only, got a W4Weight")
     kind, plan, w = _pick_kernel(x, w, plan, epi, groups if grouped else None)
     if out is None:
         dt = torch.float32 if epi == "f32" else x.dtype
@@ -581,8 +683,7 @@ def linear(x, w, bias=None, epi: str = "none", out=None):
 
 def _splitk_plan(x, w):
     """A split-K plan for a GEMM whose partial sums feed a fused reduce, or None."""
-    if not _use_native(x) or x.stride(-1) != 1 or not (isinstance(w, Fp8Weight)
-                                                       or w.stride(-1) == 1):
+    if not _use_native(x) or x.stride(-1) != 1 or not _inner_contig(w):
         return None
     M, K = x.shape
     p = G.plan(M, w.shape[0], K, "splitk", G.wdt(w))

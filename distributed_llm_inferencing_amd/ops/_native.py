@@ -80,6 +80,11 @@ _SIGS = {
     # groups, tile_list, max_items, stream
     "dli_gemm_fp8_stream_grouped": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, I, P, P, I, P, I,
                                     P],
+    # 4-bit group-scaled weights: dli_gemv_fp8 / dli_gemv_fused_fp8's arguments with the packed
+    # nibbles and the sz words for q and the scales; the bf16 image (q_packed, sz, out, N, K)
+    "dli_gemv_w4": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    "dli_gemv_fused_w4": [P, I, P, F, P, P, I, I, P, I, I, I, I, I, I, I, P, P],
+    "dli_dequant_w4": [P, P, P, I, I, P],
     "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

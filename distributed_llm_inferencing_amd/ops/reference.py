@@ -143,6 +143,82 @@ def dequantize_experts(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) ->
     return torch.stack([dequantize_weight(q[e], s[e], dtype) for e in range(q.shape[0])])
 
 
+# 4-bit group-scaled weights (weight-only "W4A16", the AWQ format): q and z in 0..15, s fp16,
+# one (s, z) per output row per W4_GROUP K-elements:
+#   W[n, k] = (float(q[n, k]) - float(z[n, k // 128])) * float(s[n, k // 128])
+# In memory (what the kernels read): ``q_packed`` uint8 [N, K / 2], as 32-bit words of 8
+# nibbles, nibble i of word w holding element 8 w + W4_ORDER[i], and ``sz`` int32 [N, K / 128],
+# the fp16 scale's bits in the low half and the zero point in bits 16..19. Scales are per row,
+# so ``cat`` and ``interleave_gate_up`` carry them along with the rows.
+W4_GROUP = 128
+W4_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+
+
+def _w4_check(shape, k: int, what: str) -> None:
+    if k % W4_GROUP:
+        raise ValueError(f"{what}: K = {k} is not a multiple of the 4-bit group size "
+                         f"{W4_GROUP} (shape {tuple(shape)})")
+
+
+def pack_w4(qint: torch.Tensor, s: torch.Tensor, z: torch.Tensor, name: str = "weight"):
+    """(q_packed uint8 [N, K / 2], sz int32 [N, K / 128]) of integers ``qint`` [N, K] in 0..15,
+    fp16 scales ``s`` and zero points ``z`` in 0..15, both [N, K / 128]."""
+    n, k = qint.shape
+    _w4_check(qint.shape, k, name)
+    g = k // W4_GROUP
+    if tuple(s.shape) != (n, g) or tuple(z.shape) != (n, g) or s.dtype != torch.float16:
+        raise ValueError(f"{name}: scales {tuple(s.shape)} {s.dtype} / zeros {tuple(z.shape)} do "
+                         f"not fit a 4-bit weight {(n, k)}: expected fp16 and integers [N, K / 128]")
+    v = qint.to(torch.int32).view(n, k // 8, 8)[:, :, list(W4_ORDER)]
+    # nibbles 2 j and 2 j + 1 of a word are byte j (little endian)
+    q_packed = (v[:, :, 0::2] | (v[:, :, 1::2] << 4)).to(torch.uint8).reshape(n, k // 2)
+    sz = s.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF | (z.to(torch.int32) << 16)
+    return q_packed.contiguous(), sz.contiguous()
+
+
+def unpack_w4(q_packed: torch.Tensor, sz: torch.Tensor):
+    """Inverse of ``pack_w4``: (qint uint8 [N, K], s fp16 [N, K / 128], z uint8 [N, K / 128])."""
+    n, k = q_packed.shape[0], q_packed.shape[1] * 2
+    _w4_check((n, k), k, "weight")
+    if q_packed.dtype != torch.uint8 or sz.dtype != torch.int32 or \
+            tuple(sz.shape) != (n, k // W4_GROUP):
+        raise ValueError(f"sz {tuple(sz.shape)} {sz.dtype} does not fit a packed 4-bit weight "
+                         f"{(n, k)} ({q_packed.dtype}): expected uint8 and int32 [N, K / 128]")
+    b = q_packed.view(n, k // 8, 4)
+    nib = torch.stack([b & 15, b >> 4], dim=-1).view(n, k // 8, 8)      # nibble order
+    qint = torch.empty_like(nib)
+    qint[:, :, list(W4_ORDER)] = nib
+    s = (sz & 0xFFFF).to(torch.int16).view(torch.float16)
+    z = ((sz >> 16) & 15).to(torch.uint8)
+    return qint.reshape(n, k), s, z
+
+
+def quantize_weight_w4(w: torch.Tensor, name: str = "weight"):
+    """(qint [N, K] uint8, s fp16 [N, K / 128], z uint8 [N, K / 128]) of one weight: asymmetric
+    round-to-nearest per row and group, s = fp16(max((max - min) / 15, tiny)),
+    z = clamp(round(-min / s), 0, 15), q = clamp(round(w / s) + z, 0, 15). Plain rounding, no
+    activation-aware calibration."""
+    n, k = w.shape
+    _w4_check(w.shape, k, name)
+    g = w.float().view(n, k // W4_GROUP, W4_GROUP)
+    lo, hi = g.amin(-1), g.amax(-1)
+    tiny = float(torch.finfo(torch.float16).tiny)
+    s = ((hi - lo) / 15).clamp(tiny, float(torch.finfo(torch.float16).max)).to(torch.float16)
+    sf = s.float()
+    z = torch.round(-lo / sf).clamp(0, 15)
+    q = (torch.round(g / sf[..., None]) + z[..., None]).clamp(0, 15)
+    return q.to(torch.uint8).view(n, k), s, z.to(torch.uint8)
+
+
+def dequantize_weight_w4(q_packed: torch.Tensor, sz: torch.Tensor,
+                         dtype=torch.float32) -> torch.Tensor:
+    """The reconstructed weight: the fp32 value (q - z) * s, rounded once to ``dtype``."""
+    qint, s, z = unpack_w4(q_packed, sz)
+    ze = z.float().repeat_interleave(W4_GROUP, dim=1)
+    se = s.float().repeat_interleave(W4_GROUP, dim=1)
+    return ((qint.float() - ze) * se).to(dtype)
+
+
 def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     """[F, K] x2 -> [2F, K] in the 16-row interleaved layout (see module doc)."""
     f, k = gate.shape

@@ -594,7 +594,8 @@ def load_ep_params(model_dir: str, cfg, expert_range, device, dtype):
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)
     # (FP8 projections and their fp32 scales stay as they are)
-    return {k: (v if v.dtype in (dtype, W.R.FP8_W) or k.endswith("_scale") else v.to(dtype))
+    return {k: (v if v.dtype in (dtype, W.R.FP8_W) or k.endswith(("_scale", "_sz"))
+                or k + "_sz" in out else v.to(dtype))
             for k, v in out.items()}
 
 

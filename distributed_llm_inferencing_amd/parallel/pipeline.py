@@ -235,7 +235,7 @@ def _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction, cap_token
     rank on one device (``DLI_SAME_DEVICE=1``) so are every other rank's — summed over the
     ranks, or 8 ranks each sizing against the empty device over-commit it (Llama-3-70B pp8 on
     one GPU ran out of memory: profiles/r6/README.md). ``fp8_weights``: the stage will hold
-    FP8 projections, whose bf16 scratch (``ops.reserve_fp8_scratch``) is allocated when the
+    FP8 or 4-bit projections, whose bf16 scratch (``ops.reserve_fp8_scratch``) is allocated when the
     model is built, after this; a model quantised at start-up is counted at its bf16 bytes,
     its peak."""
     pending = W.fp8_scratch_bytes(cfg) if fp8_weights else 0
@@ -784,8 +784,10 @@ def build_stage(cfg: ModelConfig, rank: int, world: int, device, max_batch: int,
         cap = _stage_capacity_blocks(cfg, plan, block_size, device, kv_fraction,
                                      cap_tokens=max_kv_tokens, vocab_slice=vs,
                                      loaded=params is not None, kv_dtype=kv_dtype,
-                                     fp8_weights=(W.resolve_weight_dtype(weight_dtype) == "fp8"
-                                                  or (params is not None and W.is_fp8(params))))
+                                     fp8_weights=(
+                                         W.resolve_weight_dtype(weight_dtype) in ("fp8", "w4")
+                                         or (params is not None
+                                             and W.params_weight_dtype(params) != "bf16")))
         t = torch.tensor([cap], dtype=torch.int64,
                          device=device if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)     # block ids are global: same pool size

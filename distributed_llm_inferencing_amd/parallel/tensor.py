@@ -33,6 +33,9 @@ from ..ops.reference import GU_GROUP
 
 def shard_param(name: str, t: torch.Tensor, cfg, rank: int, world: int) -> torch.Tensor:
     hd, hq, hkv = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+    if name.endswith("_sz") or t.dtype == torch.uint8:
+        raise ValueError(f"{name}: tensor parallel mode slices weights and cannot slice a 4-bit "
+                         "group-scaled one")
     if t.dtype == torch.float8_e4m3fn or name.endswith("_scale"):
         raise ValueError(f"{name}: tensor parallel mode slices weights and cannot slice an FP8 "
                          "block-scaled one (its scales cover 128-column blocks)")
@@ -81,6 +84,9 @@ class TensorParallelEngine:
     def __init__(self, model: str, device, max_batch: int = 256, max_model_len: int = 2048,
                  seed: int = 0, num_blocks: Optional[int] = None, dtype=torch.bfloat16,
                  max_prefill_tokens: int = 16384, weight_dtype: Optional[str] = None):
+        if W.resolve_weight_dtype(weight_dtype) == "w4":
+            raise ValueError("tensor parallel mode has no 4-bit weights (weight_dtype w4): it "
+                             "slices the projections across ranks")
         if W.resolve_weight_dtype(weight_dtype) == "fp8":
             raise ValueError("tensor parallel mode has no FP8 weights (weight_dtype fp8): it "
                              "slices the projections across ranks")

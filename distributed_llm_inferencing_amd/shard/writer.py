@@ -46,6 +46,10 @@ def export_shards(model_name: str, num_shards: int, output_dir: str = "model_sha
         from ..models.hf import config_from_hf, hf_weight_dtype
         hf_cfg = json.loads((Path(hf_dir) / "config.json").read_text())
         cfg = config_from_hf(hf_cfg, model_name, sliding_window=True)
+        if hf_weight_dtype(hf_cfg) == "w4":
+            raise ValueError(f"{hf_dir}: a 4-bit AWQ checkpoint (quantization_config) cannot be "
+                             "sharded: the shard writer exports bf16 / fp16 / fp32 stages only. "
+                             "Serve it whole from the model cache")
         if hf_weight_dtype(hf_cfg) == "fp8":
             raise ValueError(f"{hf_dir}: an FP8 checkpoint (quantization_config) cannot be "
                              "sharded: the shard writer exports bf16 / fp16 / fp32 stages only. "

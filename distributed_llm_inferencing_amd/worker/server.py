@@ -83,7 +83,7 @@ class WorkerState:
         from ..engine.kv_cache import resolve_kv_dtype
         self.engine_kwargs["kv_dtype"] = resolve_kv_dtype(
             self.engine_kwargs.get("kv_dtype") or getattr(settings, "kv_cache_dtype", None))
-        # likewise the weight dtype (bf16 | fp8; None: a checkpoint's own)
+        # likewise the weight dtype (bf16 | fp8 | w4; None: a checkpoint's own)
         from ..models.weights import resolve_weight_dtype
         self.engine_kwargs["weight_dtype"] = resolve_weight_dtype(
             self.engine_kwargs.get("weight_dtype") or getattr(settings, "weight_dtype", "")
@@ -674,7 +674,7 @@ def main(argv=None):
     ap.add_argument("--max-batch", type=int, default=None)
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
-    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8", "w4"],
                     help="fp8: quantise the llama-family projections and experts to block-scaled "
                          "FP8 "
                          "(default: WEIGHT_DTYPE, or the checkpoint's own)")

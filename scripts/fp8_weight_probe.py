@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""The weight stream with bf16 and FP8 block-scaled weights, per Llama-3-8B projection, timed as
+"""The weight stream with bf16, FP8 block-scaled and 4-bit group-scaled weights, per Llama-3-8B projection, timed as
 graph replays over cold weights (a different weight copy per call, together larger than the
 Infinity Cache, as bench_decode_tiles.py does). Microseconds and weight GB/s (the weight's
 bytes, scales included, over the time), one JSON line each.
 
     python scripts/fp8_weight_probe.py [--m 1,2,3,4,8,16,32,64,128,256,512]
                                        [--shapes qkv,o,gate_up,down]
+                                       [--weight-dtype bf16,fp8,w4]
 
 M <= 4: every GEMV plan (tile x split-K) of each (projection, M, weight dtype), the fastest
 reported. Epilogues are the batch-1 chain's: QKV bf16 rows, O and down adding into the residual
@@ -16,6 +17,9 @@ the MFMA weight-stream tiles, split plans with their reduce kernel), one for the
 of the dequantise + bf16-GEMM path on the same FP8 weight ("fp8_dequant": the dequantise
 kernel's time and its bytes are in it; the rate still counts the FP8 bytes) and one for the
 fastest plan of the bf16-weight GEMM ("bf16"). Epilogues: bf16 rows, gate/up with SiLU*up.
+
+A 4-bit weight ("w4") past M = 4 has the dequantise path only: one line, "w4_dequant", for its
+fastest plan, the dequantise kernel's time in it.
 
 64 < M <= 512: the same three paths, with every plan of the FP8 LDS tiles 72 / 73
 (``G.fp8_tile_plans``, ``path`` "fp8_tiles") in the place of the stream plans. These lines also
@@ -60,6 +64,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", default="1,2,3,4")
     ap.add_argument("--shapes", default="qkv,o,gate_up,down")
+    ap.add_argument("--weight-dtype", default="bf16,fp8")
     ap.add_argument("--iters", type=int, default=6)
     a = ap.parse_args()
     from distributed_llm_inferencing_amd import ops
@@ -72,10 +77,18 @@ def main():
     for name in a.shapes.split(","):
         N, K, epi = SHAPES[name]
         wb = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
-        q, s = R.quantize_weight(wb)
-        w8 = ops.Fp8Weight(q, R.group_scales(R.row_scales(s, N)))
-        for dt, w0, nbytes in (("bf16", wb, N * K * 2),
-                               ("fp8", w8, N * K + w8.scale.numel() * 4)):
+        for dt in a.weight_dtype.split(","):
+            if dt == "bf16":
+                w0, nbytes = wb, N * K * 2
+            elif dt == "fp8":
+                q, s = R.quantize_weight(wb)
+                w0 = ops.Fp8Weight(q, R.group_scales(R.row_scales(s, N)))
+                nbytes = N * K + w0.scale.numel() * 4
+            elif dt == "w4":
+                w0 = ops.W4Weight(*R.pack_w4(*R.quantize_weight_w4(wb)))
+                nbytes = N * K // 2 + w0.sz.numel() * 4
+            else:
+                ap.error(f"--weight-dtype {dt}: expected bf16, fp8 or w4")
             n_copies = max(2, min(16, -(-(1 << 30) // nbytes)))
             ws_ = [w0] + [w0.clone() for _ in range(n_copies - 1)]
             for M in ms_:
@@ -98,8 +111,8 @@ def main():
                         best = (ms, p)
                 if best is not None:
                     line(name, N, K, epi, M, dt, best[1], best[0], nbytes, n_copies)
-            del ws_
-        del wb, w8
+            del ws_, w0
+        del wb
 
 
 def mid_batch(ops, G, name, N, K, epi, M, dt, ws_, x, nbytes, iters):
@@ -122,7 +135,7 @@ def mid_batch(ops, G, name, N, K, epi, M, dt, ws_, x, nbytes, iters):
         if ms is not None and (best is None or ms < best[0]):
             best = (ms, p)
     if best is not None:
-        line(name, N, K, epi, M, "fp8_dequant" if dt == "fp8" else "bf16", best[1], best[0],
+        line(name, N, K, epi, M, dt if dt == "bf16" else dt + "_dequant", best[1], best[0],
              nbytes, len(ws_))
 
 
