@@ -277,8 +277,10 @@ class W4Weight:
     ``sz`` int32 [N, K / 128], W[n, k] = (q[n, k] - z[n, k // 128]) * s[n, k // 128]
     (``reference.dequantize_weight_w4``, which also defines the nibble order and the sz word).
     Looks like its [N, K] tensor to the planner; the linear ops stream it through the W4 GEMV
-    kernels at M <= ``G.GEMV_MAX_M`` (``gemv_ok``) and run every other shape on its bf16 image
-    (``bf16()``: one dequantise pass into the scratch ``Fp8Weight.bf16`` uses, per call)."""
+    kernels at M <= ``G.GEMV_MAX_M`` (``gemv_ok``), through the W4 MFMA stream tiles up to
+    ``G.W4_STREAM_MAX_M`` rows where the autotuner pinned one (``mfma_ok``), and run every other
+    shape on its bf16 image (``bf16()``: one dequantise pass into the scratch
+    ``Fp8Weight.bf16`` uses, per call)."""
     __slots__ = ("q_packed", "sz")
     act_dtype = torch.bfloat16
     wdt = "w4"                           # the weight-dtype part of a plan key (``G.wdt``)
@@ -347,6 +349,13 @@ class W4Weight:
         K = self.shape[1]
         return (M <= G.GEMV_MAX_M and p.tile in G.GEMV_TILES and K % p.splits == 0
                 and (K // p.splits) % G.W4_CHUNK == 0)
+
+    def mfma_ok(self, M: int, p: G.GemmPlan) -> bool:
+        """Whether the W4 MFMA weight stream (``dli_gemm_w4_stream``) takes this call: one of
+        its tiles, ``G.GEMV_MAX_M`` < M <= ``G.W4_STREAM_MAX_M``, and every K slice in whole
+        128-column groups (``G.tile_slices_ok``)."""
+        return (p.tile in G.W4_STREAM_TILES and G.GEMV_MAX_M < M <= G.W4_STREAM_MAX_M
+                and G.tile_slices_ok(self.shape[1], p.splits))
 
 
 # the quantised 2-D projections: a stream of their own at M <= 4, ``bf16()`` for the rest
@@ -469,6 +478,8 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
     """The one choice of a GEMM's native family: (kind, plan, weight) with kind "stream"
     (``w`` an ``Fp8Weight`` on the MFMA weight stream), "fp8_tiles" (on the FP8 LDS tiles),
     "gemv_fp8" (on the FP8 GEMV stream), "gemv_w4" (``w`` a ``W4Weight`` on the W4 GEMV stream)
+    "w4_stream" (on the W4 MFMA weight stream, ``G.W4_STREAM_TILES``; such a tile forced on
+    anything but a ``W4Weight`` is an error)
     or "gemm" (``w`` a plain tensor: the bf16 image of an ``Fp8Weight`` / ``W4Weight`` none of
     them takes, dequantised here, once). A stream or FP8 tile plan the
     call cannot take (a cached plan met another M, an odd K, a grouped call) gives way to a
@@ -478,14 +489,22 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
     fp8 = isinstance(w, Fp8Weight)
     w4 = isinstance(w, W4Weight)
     fp8_tile = p.tile in G.FP8_STREAM_TILES or p.tile in G.FP8_TILE_TABLE
-    if not fp8 and not w4 and not fp8_tile:
+    w4_tile = p.tile in G.W4_STREAM_TILES
+    if not fp8 and not w4 and not fp8_tile and not w4_tile:
         return "gemm", p, w
     M, K = x.shape
     fp8_form = groups is None and epi in G.FP8_STREAM_EPIS
-    kind = None if w4 else _fp8_plan(x, w, p, fp8_form)     # (a W4Weight has no MFMA stream)
+    if w4_tile:
+        if not w4:
+            raise ValueError(f"GEMM tile {p.tile} streams 4-bit group-scaled weights "
+                             f"(ops.W4Weight) only, got a {w.dtype} tensor")
+        kind = "w4_stream" if (fp8_form and w.mfma_ok(M, p) and x.stride(0) % 8 == 0
+                               and x.data_ptr() % 16 == 0) else None
+    else:
+        kind = None if w4 else _fp8_plan(x, w, p, fp8_form)   # (no FP8 tile takes a W4Weight)
     if kind is not None:
         return kind, p, w
-    if fp8_tile:
+    if fp8_tile or w4_tile:
         if groups is not None:
             p = G.GemmPlan("dli", G.grouped_tile(M, groups), 1)
         elif keep_splits:
@@ -499,7 +518,8 @@ def _pick_kernel(x, w, p: G.GemmPlan, epi: str, groups: Optional[int] = None,
 
 # the entry of each kind with the FP8 argument list (``_launch_gemm``)
 _FP8_ENTRY = {"stream": "dli_gemm_fp8_stream", "fp8_tiles": "dli_gemm_fp8_tiles",
-              "gemv_fp8": "dli_gemv_fp8", "gemv_w4": "dli_gemv_w4"}
+              "gemv_fp8": "dli_gemv_fp8", "gemv_w4": "dli_gemv_w4",
+              "w4_stream": "dli_gemm_w4_stream"}
 
 
 def _wq_args(w):
@@ -695,7 +715,7 @@ def _split_slabs(x, w, plan: Optional[G.GemmPlan] = None, ws=None):
     the plan's split-K partial slabs in the workspace (no output tensor: the consumer reduces
     them), or None where the plan (``plan`` if forced, else the "splitk" plan of the shape)
     does not split. The format the consumer must read: 1 = fp16 x 1/16 (the MFMA families'
-    EPI "slab16" store, half the bytes), 0 = fp32 (the GEMV tiles, the FP8 stream tiles and
+    EPI "slab16" store, half the bytes), 0 = fp32 (the GEMV tiles, the FP8 and W4 stream tiles,
     the FP8 LDS tiles 72 / 73, the 4-wave family). ``x`` may be a ``NormedRows``: the GEMV with the norm in its prologue where the
     plan has one, else the materialised norm. ``ws``: the caller's own slab buffer."""
     normed = isinstance(x, NormedRows)

@@ -18,8 +18,10 @@ of the dequantise + bf16-GEMM path on the same FP8 weight ("fp8_dequant": the de
 kernel's time and its bytes are in it; the rate still counts the FP8 bytes) and one for the
 fastest plan of the bf16-weight GEMM ("bf16"). Epilogues: bf16 rows, gate/up with SiLU*up.
 
-A 4-bit weight ("w4") past M = 4 has the dequantise path only: one line, "w4_dequant", for its
-fastest plan, the dequantise kernel's time in it.
+A 4-bit weight ("w4") at 4 < M <= 64: one line for EVERY W4 stream plan (``path`` "w4_stream":
+the MFMA nibble-stream tiles 74 / 75, ``G.w4_stream_plans``) and one, "w4_dequant", for the
+fastest plan of its dequantise path, the dequantise kernel's time in it; past 64 rows the
+dequantise path only.
 
 64 < M <= 512: the same three paths, with every plan of the FP8 LDS tiles 72 / 73
 (``G.fp8_tile_plans``, ``path`` "fp8_tiles") in the place of the stream plans. These lines also
@@ -129,6 +131,11 @@ def mid_batch(ops, G, name, N, K, epi, M, dt, ws_, x, nbytes, iters):
                 ms = time_plan(p)
                 if ms is not None:
                     line(name, N, K, epi, M, path, p, ms, nbytes, len(ws_))
+    if dt == "w4":
+        for p in G.w4_stream_plans(M, N, K, epi):
+            ms = time_plan(p)
+            if ms is not None:
+                line(name, N, K, epi, M, "w4_stream", p, ms, nbytes, len(ws_))
     best = None
     for p in G.candidate_plans(M, N, K, epi):
         ms = time_plan(p)
