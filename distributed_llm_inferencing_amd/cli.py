@@ -202,8 +202,9 @@ def _serve_expert(argv):
                          "reads all attention tensors and only its own experts' rows")
     ap.add_argument("--kv-dtype", default=None, choices=["bf16", "fp8"],
                     help="element type of the paged KV cache (default: KV_CACHE_DTYPE, bf16)")
-    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8"],
-                    help="fp8: block-scaled FP8 projection and expert weights (Qwen3-MoE "
+    ap.add_argument("--weight-dtype", default=None, choices=["bf16", "fp8", "w4"],
+                    help="fp8: block-scaled FP8 projection and expert weights; w4: 4-bit "
+                         "group-scaled ones (Qwen3-MoE "
                          "models; default: WEIGHT_DTYPE, or as the checkpoint holds them)")
     a = ap.parse_args(argv)
     from . import launch

@@ -71,20 +71,22 @@ class TransformerLM:
     def _layer_params(self, i: int) -> dict:
         """Layer ``i``'s tensors by short name; an FP8 projection and its ``_scale`` tensor
         (models/weights.py) as one ``ops.Fp8Weight``, an expert stack's as one
-        ``ops.Fp8Experts``."""
+        ``ops.Fp8Experts``; 4-bit nibbles and their ``_sz`` words as one ``ops.W4Weight`` or,
+        for an expert stack, one ``ops.W4Experts``."""
         pre = f"layers.{i}."
         lp = {k[len(pre):]: v for k, v in self.params.items() if k.startswith(pre)}
         for k in [k for k in lp if k + "_scale" in lp]:
             pair = ops.Fp8Experts if lp[k].dim() == 3 else ops.Fp8Weight
             lp[k] = pair(lp[k], lp.pop(k + "_scale"))
         for k in [k for k in lp if k + "_sz" in lp]:      # 4-bit: packed nibbles + sz words
-            lp[k] = ops.W4Weight(lp[k], lp.pop(k + "_sz"))
+            pair = ops.W4Experts if lp[k].dim() == 3 else ops.W4Weight
+            lp[k] = pair(lp[k], lp.pop(k + "_sz"))
         return lp
 
     def _bind_layers(self) -> None:
         self.layers = [self._layer_params(i) for i in range(self.layer_start, self.layer_end)]
         fp8 = [w.numel() for lp in self.layers for w in lp.values()
-               if isinstance(w, (ops.Fp8Weight, ops.Fp8Experts, ops.W4Weight))]
+               if isinstance(w, (ops.Fp8Weight, ops.Fp8Experts, ops.W4Weight, ops.W4Experts))]
         if fp8:      # the bf16 scratch of the dequantise-then-GEMM path, before the KV pool
             ops.reserve_fp8_scratch(self.device, max(fp8))
 
@@ -103,8 +105,8 @@ class TransformerLM:
         return self
 
     def quantize_w4(self) -> "TransformerLM":
-        """Quantise the four projections of every dense llama-family layer to 4-bit
-        group-scaled weights in place of their bf16 tensors (``weights.quantize_params``)."""
+        """Quantise the four projections of every llama-family layer (of Qwen3-MoE the expert
+        stacks included) to 4-bit group-scaled weights in place of their bf16 tensors (``weights.quantize_params``)."""
         self.layers = []
         W.quantize_params(self.cfg, self.params, inplace=True, weight_dtype="w4")
         self._bind_layers()

@@ -15,6 +15,8 @@ llama / mixtral (per layer ``layers.{i}.``):
     moe:   router [E, D], w_gu [E, 2F, D], w_down [E, D, F]
     FP8 expert stacks: w_gu / w_down float8_e4m3fn with ``<name>_scale`` [E, N/16, ceil(K/128)]
     (every expert quantised by itself), paired into an ``ops.Fp8Experts``; the router is bf16
+    4-bit expert stacks (Qwen3-MoE): w_gu / w_down uint8 [E, N, K/2] with int32 ``<name>_sz``
+    [E, N, K/128], paired into an ``ops.W4Experts``; the router is bf16
 gpt2 (per layer): ln1_w, ln1_b, wqkv [3D, D], bqkv [3D], wo [D, D], bo [D], ln2_w, ln2_b,
     w_fc [F, D], b_fc [F], w_proj [D, F], b_proj [D]
 globals: embed [V, D], (gpt2) pos_embed [P, D], final_norm [D], (gpt2) final_norm_b [D],
@@ -119,8 +121,9 @@ def random_init(shapes: Dict[str, tuple], device, dtype=torch.bfloat16, seed: in
 
 
 def _is_expert_tensor(name: str) -> bool:
-    """An expert stack or the FP8 scales that go with it."""
-    return name.endswith((".w_gu", ".w_down", ".w_gu_scale", ".w_down_scale"))
+    """An expert stack, or the FP8 scales or 4-bit scale / zero-point words that go with it."""
+    return name.endswith((".w_gu", ".w_down", ".w_gu_scale", ".w_down_scale", ".w_gu_sz",
+                          ".w_down_sz"))
 
 
 def slice_experts(name: str, t: torch.Tensor, expert_range: Optional[tuple]) -> torch.Tensor:
@@ -195,12 +198,13 @@ def check_fp8_model(cfg: ModelConfig) -> None:
 
 
 def check_w4_model(cfg: ModelConfig) -> None:
-    """4-bit weights exist for the dense llama-family layers: no experts, no gpt2."""
+    """4-bit weights exist for the dense llama-family layers and for Qwen3-MoE (expert stacks
+    as ``ops.W4Experts``): no other MoE model, no gpt2."""
     if cfg.arch == "gpt2":
         raise ValueError(f"{cfg.name}: weight_dtype w4 is not available for gpt2 (arch) models")
-    if cfg.is_moe:
+    if cfg.is_moe and not cfg.qk_norm:
         raise ValueError(f"{cfg.name}: weight_dtype w4 with num_experts={cfg.num_experts}: "
-                         "there are no 4-bit expert kernels")
+                         "4-bit expert weights are quantised for Qwen3-MoE models only")
 
 
 def apply_weight_dtype(model, want: Optional[str]) -> None:
@@ -208,8 +212,9 @@ def apply_weight_dtype(model, want: Optional[str]) -> None:
     quantises a bf16 model's projections (refused for gpt2, and among the MoE models for all
     but Qwen3-MoE: a Mixtral holds FP8 experts only where its parameters come quantised,
     ``quantize_params``); an FP8 checkpoint sets the dtype by itself, and an explicit "bf16"
-    for one is an error, not a silent dequantise. "w4" quantises a bf16 dense llama-family
-    model to 4-bit group-scaled weights (``quantize_params``); a 4-bit (AWQ) checkpoint sets
+    for one is an error, not a silent dequantise. "w4" quantises a bf16 dense llama-family or
+    Qwen3-MoE model (attention projections and every expert's gate/up and down; every other
+    MoE model is refused) to 4-bit group-scaled weights (``quantize_params``); a 4-bit (AWQ) checkpoint sets
     the dtype by itself, and neither quantised format is converted into the other."""
     have = model.weight_dtype
     if want is not None and want != have and have != "bf16" and "w4" in (want, have):
@@ -277,7 +282,8 @@ def _quantize_proj(w: torch.Tensor, leaf: str, name: str):
 
 def _quantize_params_w4(cfg: ModelConfig, params, out) -> None:
     """``quantize_params`` for "w4": per-row scales, so every fused projection is quantised as
-    it stands (``reference.quantize_weight_w4`` -> ``pack_w4``)."""
+    it stands (``reference.quantize_weight_w4`` -> ``pack_w4``); an expert stack [E, N, K]
+    expert by expert into ``<name>`` [E, N, K/2] + ``<name>_sz`` [E, N, K/128]."""
     check_w4_model(cfg)
     for name in [k for k in params if k.rsplit(".", 1)[-1] in FP8_PROJECTIONS]:
         w = params[name]
@@ -285,7 +291,14 @@ def _quantize_params_w4(cfg: ModelConfig, params, out) -> None:
             continue
         if w.dtype == R.FP8_W:
             raise ValueError(f"{name}: an FP8 projection is not requantised to 4 bits")
-        out[name], out[name + "_sz"] = R.pack_w4(*R.quantize_weight_w4(w, name), name)
+        if w.dim() == 3:
+            qs = [R.pack_w4(*R.quantize_weight_w4(w[e], f"{name}[{e}]"), f"{name}[{e}]")
+                  for e in range(w.shape[0])]
+            out[name] = torch.stack([q for q, _ in qs])
+            out[name + "_sz"] = torch.stack([s for _, s in qs])
+            del qs
+        else:
+            out[name], out[name + "_sz"] = R.pack_w4(*R.quantize_weight_w4(w, name), name)
         del w
 
 
@@ -298,7 +311,8 @@ def quantize_params(cfg: ModelConfig, params: Dict[str, torch.Tensor], inplace: 
     each bf16 tensor replaced as soon as it is quantised (a caller that holds no other
     reference then never has the bf16 and the FP8 model in memory together).
     ``weight_dtype`` "w4" (also accepted in ``inplace``'s position): the same four projections
-    of the dense layers as 4-bit group-scaled weights, ``<name>`` uint8 + ``<name>_sz``."""
+    (a Qwen3-MoE layer's expert stacks included, every expert by itself) as 4-bit group-scaled
+    weights, ``<name>`` uint8 + ``<name>_sz``."""
     if isinstance(inplace, str):
         inplace, weight_dtype = False, inplace
     if weight_dtype not in ("fp8", "w4"):

@@ -432,18 +432,110 @@ class Fp8Experts:
                      _st())
         return out
 
-    def stream_ok(self, rows: int, groups: int, p: G.GemmPlan) -> bool:
+    def stream_ok(self, rows: int, groups: int, p: G.GemmPlan, epi: str = "none") -> bool:
         """Whether the grouped FP8 stream takes ``rows`` permuted rows over ``groups`` experts
-        under ``p``: one of its tiles, unsplit, K in whole 16-element chunks, and a tile list
-        (``G.max_items`` at ``G.fp8_grouped_bm``) that fits one grid dimension."""
+        under ``p``: one of its tiles, unsplit, K in whole 16-element chunks, whole 32-row
+        gate/up pairs for ``epi`` "silu_mul", and a tile list (``G.max_items`` at
+        ``G.fp8_grouped_bm``) that fits one grid dimension."""
         return (p.tile in G.FP8_STREAM_TILES and p.splits == 1 and rows > 0
+                and (epi != "silu_mul" or self.q.shape[1] % 32 == 0)
                 and groups == self.q.shape[0] and G.stream_slices_ok(self.q.shape[2], 1)
                 and G.max_items(rows, groups, G.fp8_grouped_bm(rows, groups)) <= 65535)
 
 
+class W4Experts:
+    """A stack of 4-bit group-scaled expert projections: ``q_packed`` uint8 [E, N, K / 2] and
+    ``sz`` int32 [E, N, K / 128], every expert a ``W4Weight`` of its own:
+    W[e, n, k] = (q[e, n, k] - z[e, n, k // 128]) * s[e, n, k // 128]. Looks like its [E, N, K]
+    tensor to ``moe_mlp`` and the planner; a decode step streams it through the grouped W4 MFMA
+    nibble stream (``dli_gemm_w4_stream_grouped``) where ``stream_ok`` holds, and every other
+    call runs the bf16 grouped GEMMs on its bf16 image (``bf16()``, the whole stack in one
+    pass)."""
+    __slots__ = ("q_packed", "sz")
+    act_dtype = torch.bfloat16
+    wdt = "w4"
+
+    def __init__(self, q_packed: torch.Tensor, sz: torch.Tensor):
+        if q_packed.dtype != torch.uint8 or q_packed.dim() != 3:
+            raise ValueError(f"W4Experts: q_packed must be a 3-D uint8 tensor, got "
+                             f"{q_packed.dtype} {tuple(q_packed.shape)}")
+        e, n, k = q_packed.shape[0], q_packed.shape[1], q_packed.shape[2] * 2
+        if k % R.W4_GROUP:
+            raise ValueError(f"W4Experts: K = {k} is not a multiple of {R.W4_GROUP}")
+        want = (e, n, k // R.W4_GROUP)
+        if sz.dtype != torch.int32 or tuple(sz.shape) != want:
+            raise ValueError(f"W4Experts: sz must be int32 {want} for a stack {(e, n, k)}, got "
+                             f"{sz.dtype} {tuple(sz.shape)}")
+        if sz.device != q_packed.device:
+            raise ValueError("W4Experts: q_packed and sz on different devices")
+        self.q_packed, self.sz = q_packed.contiguous(), sz.contiguous()
+
+    @property
+    def shape(self):
+        e, n, k2 = self.q_packed.shape
+        return torch.Size((e, n, k2 * 2))
+
+    @property
+    def device(self):
+        return self.q_packed.device
+
+    @property
+    def dtype(self):
+        return self.q_packed.dtype
+
+    def dim(self) -> int:
+        return 3
+
+    def numel(self) -> int:
+        return self.q_packed.numel() * 2
+
+    def element_size(self) -> float:
+        return 0.5
+
+    def clone(self) -> "W4Experts":
+        return W4Experts(self.q_packed.clone(), self.sz.clone())
+
+    def to(self, device) -> "W4Experts":
+        return W4Experts(self.q_packed.to(device), self.sz.to(device))
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        e, n, k = self.shape
+        if e * n == 0:
+            return torch.empty(e, n, k, dtype=dtype, device=self.device)
+        return R.dequantize_weight_w4(self.q_packed.view(e * n, k // 2),
+                                      self.sz.view(e * n, -1), dtype).view(e, n, k)
+
+    def bf16(self) -> torch.Tensor:
+        """The bf16 stack [E, N, K]: on the GPU a view of the per-device scratch of
+        ``Fp8Weight.bf16`` (same validity rule), filled by one ``dli_dequant_w4`` call on the
+        [E * N, K] view (the scales are per row, so no group straddles two experts)."""
+        if not self.q_packed.is_cuda:
+            return self.dequantize(torch.bfloat16)
+        e, n, k = self.shape
+        dev = self.q_packed.device
+        reserve_fp8_scratch(dev, e * n * k)
+        out = _fp8_scratch[(dev.type, dev.index)][:e * n * k].view(e, n, k)
+        _native_call("dli_dequant_w4", _p(self.q_packed), _p(self.sz), _p(out), e * n, k, _st())
+        return out
+
+    def stream_ok(self, rows: int, groups: int, p: G.GemmPlan, epi: str = "none") -> bool:
+        """Whether the grouped W4 stream takes ``rows`` permuted rows over ``groups`` experts
+        under ``p``: one of its tiles, unsplit, N in whole 16-row groups (32-row gate/up pairs
+        for ``epi`` "silu_mul"; K is a multiple of 128 by construction), and a tile list
+        (``G.max_items`` at ``G.fp8_grouped_bm``) that fits one grid dimension."""
+        e, n, _ = self.shape
+        return (p.tile in G.W4_STREAM_TILES and p.splits == 1 and rows > 0 and groups == e
+                and n % (32 if epi == "silu_mul" else 16) == 0
+                and G.max_items(rows, groups, G.fp8_grouped_bm(rows, groups)) <= 65535)
+
+
+# the quantised expert stacks: a grouped stream of their own in a decode step, ``bf16()`` else
+_QUANT_EXPERTS = (Fp8Experts, W4Experts)
+
+
 def _dense(w):
     """The tensor the bf16 kernels (or, off the GPU, the reference ops) read for ``w``."""
-    if isinstance(w, (Fp8Weight, Fp8Experts, W4Weight)):
+    if isinstance(w, (Fp8Weight, W4Weight) + _QUANT_EXPERTS):
         return w.bf16() if w.device.type == "cuda" else w.dequantize(torch.float32)
     return w
 
@@ -1253,7 +1345,8 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
     prefill = (n >= _MOE_PREFILL_ROWS * E_local
                and not torch.cuda.is_current_stream_capturing())
     rows = plan_rows if plan_rows is not None else n
-    # FP8 expert stacks (Fp8Experts): a decode step streams them (dli_gemm_fp8_stream_grouped)
+    # quantised expert stacks (Fp8Experts, W4Experts): a decode step streams them
+    # (dli_gemm_fp8_stream_grouped, dli_gemm_w4_stream_grouped: grouped_stream)
     # where the plan is a stream tile the call can take; else the bf16 plan below runs on the
     # stack's bf16 image, dequantised right before its GEMM (one scratch for both stacks)
     sbm = G.fp8_grouped_bm(rows, E_local)
@@ -1304,7 +1397,7 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
         _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
         return out
     if st_gu:                            # token rows read through the permutation, as below
-        grouped_fp8_stream(x, w_gu, p_gu, "silu_mul", act, offsets, n, sbm, lists[sbm], src)
+        grouped_stream(x, w_gu, p_gu, "silu_mul", act, offsets, n, sbm, lists[sbm], src)
     elif p_gu.splits == 1 and p_gu.tile in G.GATHER_TILES and x.is_contiguous():
         w_gu = _stack(w_gu)
         # the gate/up GEMM reads the token rows in place through the permutation (no gathered
@@ -1322,7 +1415,7 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
                      rows_per_group=n, plan=p_gu, tile_list=tl_gu)
     if st_dn:
         y = torch.empty(max(n, 1), D, dtype=x.dtype, device=dev)
-        grouped_fp8_stream(act, w_down, p_dn, "none", y, offsets, n, sbm, lists[sbm])
+        grouped_stream(act, w_down, p_dn, "none", y, offsets, n, sbm, lists[sbm])
         out = torch.empty_like(x)
         _native_call("dli_moe_combine", _p(out), _p(y), _p(topk_w), _p(pos), T, k, D, _st())
         return out
@@ -1345,45 +1438,59 @@ def moe_mlp(x, w_gu, w_down, topk_w, topk_ids, expert_offset: int = 0,
 
 def _stack(w):
     """The [E, N, K] tensor the bf16 grouped GEMMs read for an expert stack."""
-    return w.bf16() if isinstance(w, Fp8Experts) else w
+    return w.bf16() if isinstance(w, _QUANT_EXPERTS) else w
 
 
 def _rows_aligned(x) -> bool:
     return x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and x.stride(-1) == 1
 
 
+# the stream tiles of the grouped entries and the one class of stack each of them reads
+_STREAM_STACK = {**{t: ("FP8 block-scaled", Fp8Experts) for t in G.FP8_STREAM_TILES},
+                 **{t: ("4-bit group-scaled", W4Experts) for t in G.W4_STREAM_TILES}}
+
+
 def _expert_plan(w, rows: int, n: int, Nn: int, K: int, epi: str, groups: int, bm: int,
                  form_ok: bool):
     """(plan, streams) of one expert projection of ``moe_mlp``: a bf16 stack's grouped plan as
-    ever; an ``Fp8Experts`` stack's plan under the FP8 key, which streams when it is a stream
-    tile that takes the call (``stream_ok``, ``form_ok``: a decode step with aligned rows)
-    and else gives way to a bf16-family plan of the dequantise path, so a stream tile id
-    never reaches ``dli_gemm``."""
-    if not isinstance(w, Fp8Experts):
-        p = G.grouped_plan(rows, Nn, K, epi, groups)
-        if p.tile in G.FP8_STREAM_TILES:
-            raise ValueError(f"GEMM tile {p.tile} streams FP8 block-scaled weights "
-                             f"(ops.Fp8Experts) only, got a {w.dtype} stack")
+    ever; an ``Fp8Experts`` / ``W4Experts`` stack's plan under its "fp8" / "w4" key, which
+    streams when it is a stream tile that takes the call (``stream_ok``, ``form_ok``: a decode
+    step with aligned rows) and else gives way to a bf16-family plan of the dequantise path, so
+    a stream tile id never reaches ``dli_gemm``. A stream tile on a stack of another class
+    (70 / 71 on anything but an ``Fp8Experts``, 74 / 75 but a ``W4Experts``) is an error."""
+    quant = isinstance(w, _QUANT_EXPERTS)
+    p = G.grouped_plan(rows, Nn, K, epi, groups, G.wdt(w) if quant else None)
+    if p.tile not in _STREAM_STACK:
         return p, False
-    p = G.grouped_plan(rows, Nn, K, epi, groups, "fp8")
-    if p.tile not in G.FP8_STREAM_TILES:
-        return p, False
-    if (form_ok and n > 0 and w.stream_ok(n, groups, p)
+    what, cls = _STREAM_STACK[p.tile]
+    if not isinstance(w, cls):
+        got = type(w).__name__ if quant else f"{w.dtype} stack"
+        raise ValueError(f"GEMM tile {p.tile} streams {what} weights (ops.{cls.__name__}) "
+                         f"only, got a {got}")
+    if (form_ok and n > 0 and w.stream_ok(n, groups, p, epi)
             and G.max_items(n, groups, bm) <= 65535):
         return p, True
     return G.grouped_plan(rows, Nn, K, epi, groups), False
 
 
-def grouped_fp8_stream(x, w: "Fp8Experts", p: G.GemmPlan, epi: str, out, offsets, n: int,
-                       bm: int, tile_list, arow=None):
+def grouped_stream(x, w, p: G.GemmPlan, epi: str, out, offsets, n: int, bm: int, tile_list,
+                   arow=None):
     """out[r] = epi(x[arow[r] or r] @ W[e(r)].T) for the ``n`` permuted rows whose experts
-    ``offsets`` delimits, on the grouped FP8 MFMA stream: ``tile_list`` = (list, max items)
-    of the align step for ``bm``-row items. Rows past ``offsets[-1]`` are not written."""
+    ``offsets`` delimits, on the grouped MFMA weight stream of ``w`` (an ``Fp8Experts`` or a
+    ``W4Experts``): ``tile_list`` = (list, max items) of the align step for ``bm``-row items.
+    Rows past ``offsets[-1]`` are not written."""
     E, Nn, K = w.shape
-    _native_call("dli_gemm_fp8_stream_grouped", _p(x), x.stride(0), _p(w.q), _p(w.scale),
-                 w.scale.stride(1), K, _p(out), out.stride(0), n, Nn, K, G.EPI[epi], p.tile,
-                 p.splits, bm, _p(arow), _p(offsets), E, _p(tile_list[0]), tile_list[1], _st())
+    if isinstance(w, W4Experts):
+        entry, q, s = "dli_gemm_w4_stream_grouped", w.q_packed, w.sz
+    else:
+        entry, q, s = "dli_gemm_fp8_stream_grouped", w.q, w.scale
+    _native_call(entry, _p(x), x.stride(0), _p(q), _p(s), s.stride(1), K, _p(out),
+                 out.stride(0), n, Nn, K, G.EPI[epi], p.tile, p.splits, bm, _p(arow),
+                 _p(offsets), E, _p(tile_list[0]), tile_list[1], _st())
     return out
+
+
+grouped_fp8_stream = grouped_stream      # (its name while FP8 stacks were the only ones)
 
 
 def moe_slab_plan(p: Optional[G.GemmPlan]) -> bool:

@@ -87,6 +87,9 @@ _SIGS = {
     "dli_dequant_w4": [P, P, P, I, I, P],
     # the W4 weight stream at 4 < M <= 64 (MFMA tiles 74 / 75): dli_gemv_w4's arguments
     "dli_gemm_w4_stream": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    # its grouped (MoE) form on the compact grid: dli_gemm_fp8_stream_grouped's arguments
+    "dli_gemm_w4_stream_grouped": [P, I, P, P, I, I, P, I, I, I, I, I, I, I, I, P, P, I, P, I,
+                                   P],
     "dli_moe_route": [P, P, P, I, I, I, I, P],
     "dli_moe_router": [P, P, P, I, P, I, I, I, I, P],
     "dli_splitk_add_rmsnorm_route": [P, P, P, I, I, I, P, F, P, I, I, P, P, P],

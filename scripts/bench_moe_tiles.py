@@ -17,6 +17,12 @@ FP8 expert stacks (``ops.Fp8Experts``, random bytes and scales): the grouped FP8
 70 / 71 at ``G.fp8_grouped_bm``, the dequantise pass + the fastest bf16 plan (the pass in the
 timing), and that bf16 plan alone on the bf16 image (what bf16 weights cost). One JSON line
 each, with the time and the FP8 weight bytes per second.
+
+    python scripts/bench_moe_tiles.py --weight-dtype w4 --model qwen3-30b-a3b --batch 64 --rounds 2
+
+The same three ways for a 4-bit stack (``ops.W4Experts``, random nibbles, scales and zero
+points; stream tiles 74 / 75), with the nibble + sz bytes per second. ``--rounds``: the whole
+sequence again, so the three ways alternate and their spread shows.
 """
 import argparse
 import itertools
@@ -33,7 +39,22 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 MODELS = {"mixtral-8x7b": (8, 4096, 14336, 2), "qwen3-30b-a3b": (128, 2048, 768, 8)}
 
 
-def fp8_probe(a, ops, G, dev):
+def quant_stack(wd, E, N, K, ops, dev):
+    """A random ``Fp8Experts`` / ``W4Experts`` stack and its bytes, built on the device."""
+    if wd == "w4":
+        q = torch.randint(0, 256, (E, N, K // 2), dtype=torch.uint8, device=dev)
+        s = torch.exp2(torch.rand(E, N, K // 128, device=dev) * 4 - 10).to(torch.float16)
+        sz = (s.view(torch.int16).to(torch.int32) & 0xFFFF) | (
+            torch.randint(0, 16, (E, N, K // 128), dtype=torch.int32, device=dev) << 16)
+        return ops.W4Experts(q, sz), q.numel() + 4 * sz.numel()
+    q = torch.empty(E, N, K, dtype=torch.float8_e4m3fn, device=dev)
+    for e in range(E):                           # (an expert at a time: no fp32 stack)
+        q[e] = torch.randn(N, K, device=dev).to(torch.float8_e4m3fn)
+    s = torch.exp2(torch.rand(E, N // 16, -(-K // 128), device=dev) * 4 - 10)
+    return ops.Fp8Experts(q, s), q.numel()
+
+
+def quant_probe(a, ops, G, dev, rnd):
     E, D, F, topk = MODELS[a.model]
     rows = a.batch * topk
     counts = np.random.default_rng(1234).multinomial(rows, [1.0 / E] * E).tolist()
@@ -41,25 +62,22 @@ def fp8_probe(a, ops, G, dev):
     bm = G.fp8_grouped_bm(rows, E)
     for which in a.which.split(","):
         N, K, epi = (D, F, "none") if which == "down" else (2 * F, D, "silu_mul")
-        q = torch.empty(E, N, K, dtype=torch.float8_e4m3fn, device=dev)
-        for e in range(E):                       # (an expert at a time: no fp32 stack)
-            q[e] = torch.randn(N, K, device=dev).to(torch.float8_e4m3fn)
-        s = torch.exp2(torch.rand(E, N // 16, -(-K // 128), device=dev) * 4 - 10)
-        w = ops.Fp8Experts(q, s)
+        wd = a.weight_dtype
+        w, nbytes = quant_stack(wd, E, N, K, ops, dev)
         x = (torch.randn(rows, K, device=dev) * 0.5).to(torch.bfloat16)
         y = torch.empty(rows, N // 2 if epi == "silu_mul" else N, dtype=torch.bfloat16,
                         device=dev)
         base = {"model": a.model, "which": which, "batch": a.batch, "rows": rows, "E": E,
-                "N": N, "K": K}
+                "N": N, "K": K, "round": rnd}
+        rate = "fp8_TBps" if wd == "fp8" else wd + "_TBps"
 
         def report(kind, ms, **kw):
-            print(json.dumps(dict(base, kind=kind, us=round(ms * 1e3, 1),
-                                  fp8_TBps=round(w.numel() / (ms * 1e-3) / 1e12, 2), **kw)),
-                  flush=True)
+            print(json.dumps(dict(base, kind=kind, us=round(ms * 1e3, 1), **kw,
+                                  **{rate: round(nbytes / (ms * 1e-3) / 1e12, 2)})), flush=True)
         tl = G.host_tile_list(counts, bm, dev)
-        for tile in sorted(G.FP8_STREAM_TILES):
+        for tile in sorted(G.GROUPED_STREAMS[wd][0]):
             p = G.GemmPlan("dli", tile, 1)
-            ms = ops.benchmark(lambda: ops.grouped_fp8_stream(x, w, p, epi, y, off, rows, bm, tl),
+            ms = ops.benchmark(lambda: ops.grouped_stream(x, w, p, epi, y, off, rows, bm, tl),
                                iters=a.iters, warmup=1)
             report("stream", ms, tile=tile, bm=bm)
         image = w.bf16()
@@ -85,12 +103,13 @@ def fp8_probe(a, ops, G, dev):
         report("dequantise+bf16", ops.benchmark(lambda: run(w.bf16), iters=a.iters, warmup=1),
                tile=tile, bm_bn=G.TILES[tile])
         report("dequantise_pass", ops.benchmark(w.bf16, iters=a.iters, warmup=1))
-        del w, q, image
+        del w, image
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8", "w4"])
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--model", default="mixtral-8x7b", choices=sorted(MODELS))
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--which", default="down,gate_up")
@@ -101,8 +120,10 @@ def main():
     from distributed_llm_inferencing_amd import ops
     from distributed_llm_inferencing_amd.ops import gemm as G
     dev = torch.device("cuda")
-    if a.weight_dtype == "fp8":
-        return fp8_probe(a, ops, G, dev)
+    if a.weight_dtype != "bf16":
+        for rnd in range(a.rounds):
+            quant_probe(a, ops, G, dev, rnd)
+        return
     E, D, F = 8, 4096, 14336
     rows = a.batch * 2
     counts = np.random.default_rng(1234).multinomial(rows, [1.0 / E] * E).tolist()
