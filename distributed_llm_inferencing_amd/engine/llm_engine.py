@@ -46,6 +46,7 @@ class EngineStats:
     waiting_sum: int = 0
     latencies: List[float] = field(default_factory=list)
     weight_dtype: str = "bf16"      # "fp8": FP8 block-scaled projection weights
+    shared_prefix: bool = False     # shared-prefix decode attention (models/model.py)
 
     def __call__(self) -> dict:
         return self.snapshot()
@@ -62,7 +63,7 @@ class EngineStats:
                 "running_sum": self.running_sum, "waiting_sum": self.waiting_sum,
                 "tokens_per_s": (self.tokens_out / self.busy_s) if self.busy_s > 0 else 0.0,
                 "p50_latency_s": pct(0.5), "p99_latency_s": pct(0.99),
-                "weight_dtype": self.weight_dtype}
+                "weight_dtype": self.weight_dtype, "shared_prefix": self.shared_prefix}
 
 
 class _HostTokens:
@@ -110,9 +111,13 @@ class LLMEngine:
                  lm: Optional[TransformerLM] = None, lookahead: Optional[bool] = None,
                  max_kv_tokens: Optional[int] = None, mixed_steps: Optional[bool] = None,
                  kv_dtype: Optional[str] = None, k_scale: float = 1.0, v_scale: float = 1.0,
-                 weight_dtype: Optional[str] = None):
+                 weight_dtype: Optional[str] = None, shared_prefix: Optional[bool] = None):
         # "bf16" | "fp8" (None: the environment variable KV_CACHE_DTYPE, default bf16)
         self.kv_dtype = resolve_kv_dtype(kv_dtype)
+        # shared-prefix decode attention (None: SHARED_PREFIX_ATTENTION=1 in the environment,
+        # default off)
+        self.shared_prefix = (os.environ.get("SHARED_PREFIX_ATTENTION", "0") == "1"
+                              if shared_prefix is None else bool(shared_prefix))
         # "bf16" | "fp8" (None: the environment variable WEIGHT_DTYPE; neither: as loaded)
         want_w = resolve_weight_dtype(weight_dtype)
         self.cfg = get_config(model, num_layers) if isinstance(model, str) else model
@@ -129,6 +134,7 @@ class LLMEngine:
                                        device=self.device)
         apply_weight_dtype(self.model, want_w)
         self.weight_dtype = self.model.weight_dtype
+        self.model.shared_prefix = self.shared_prefix
         max_model_len = min(max_model_len, cfg.max_position)
         if num_blocks is None:
             # KV pool sized from free HBM, optionally capped
@@ -149,7 +155,8 @@ class LLMEngine:
         self.runner = StageRunner(self.model, self.kv, max_batch, self.scheduler.table_width,
                                   use_graphs=use_graphs)
         self.tokenizer = load_tokenizer(cfg, tokenizer_path)
-        self.stats = EngineStats(weight_dtype=self.weight_dtype)
+        self.stats = EngineStats(weight_dtype=self.weight_dtype,
+                                 shared_prefix=self.shared_prefix)
         self.timer = StepTimer()
         self.spans = SpanLog()
         self._ids = itertools.count()

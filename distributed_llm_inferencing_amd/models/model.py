@@ -54,6 +54,13 @@ class TransformerLM:
         # normed hidden state; every stage holds a vocab slice of the head
         self.vocab_parallel = False
         self.vocab_offset = 0
+        # shared-prefix decode attention (ops.shared_prefix_plan): the KV blocks that the
+        # decode rows of a step share are read once per tile of sequences. Off by default;
+        # LLMEngine(shared_prefix=...) or SHARED_PREFIX_ATTENTION=1 turn it on.
+        self.shared_prefix = False
+        # diagnostic hook, not part of the switch: the plan of the last step that built one
+        # (under graph capture: the captured plan tensors, which a replay refreshes)
+        self.last_shared_plan: Optional[ops.SharedPrefixPlan] = None
         self._bind_layers()
 
     # ------------------------------------------------------------------ construction
@@ -188,6 +195,18 @@ class TransformerLM:
         defer = (not b.is_prefill and self.tp_reduce is None and not cfg.is_moe
                  and ops.deferred_norm_ok(x))
         kvs = self._kv_scales(kv_caches)
+        # shared-prefix attention: one plan per step for its decode rows, read by every layer
+        # (it has no fused QKV prologue: the layers take the two-kernel path, as an FP8 cache).
+        # Only where ops.decode_attention has the kernels (ops.shared_prefix_ok).
+        shared = None
+        nd = b.num_decode if b.is_prefill else x.shape[0]
+        if (self.shared_prefix and kv_caches and b.block_tables is not None
+                and ops.shared_prefix_ok(nd, cfg.num_heads, cfg.num_kv_heads, cfg.head_dim,
+                                         cfg.sliding_window,
+                                         kv_caches[0][0].dtype == R.FP8_KV)):
+            shared = ops.shared_prefix_plan(b.block_tables[:nd], b.context_lens[:nd],
+                                            kv_caches[0][0].shape[2])
+            self.last_shared_plan = shared
         for li, lp in enumerate(self.layers):
             kc, vc = kv_caches[li] if kv_caches else (None, None)
             if pending is not None:          # MoE output of the previous layer
@@ -197,7 +216,8 @@ class TransformerLM:
             # Qwen2's QKV bias / Qwen3's per-head q,k RMSNorm: inputs of the same RoPE kernels
             bqkv = lp["bqkv"] if cfg.qkv_bias else None
             qkn = (lp["q_norm"], lp["k_norm"], eps) if cfg.qk_norm else None
-            if not b.is_prefill:             # decode: reduce + RoPE + KV write + attention fused
+            # decode: reduce + RoPE + KV write + attention fused
+            if not b.is_prefill and shared is None:
                 attn = ops.linear_rope_attention(h, lp["wqkv"], b.positions, b.slot_mapping,
                                                  self.cos_sin, kc, vc, b.block_tables,
                                                  b.context_lens, b.max_context, cfg.num_heads,
@@ -209,7 +229,7 @@ class TransformerLM:
                                             self.cos_sin, kc, vc, cfg.num_heads,
                                             cfg.num_kv_heads, cfg.head_dim, bias=bqkv,
                                             qk_norm=qkn, k_scale=kvs[0], v_scale=kvs[1])
-                attn = self._attend(qkv, b, kc, vc, kvs)
+                attn = self._attend(qkv, b, kc, vc, kvs, shared)
             if cfg.is_moe and self.tp_reduce is None and not defer:
                 # O projection + add + RMSNorm with the MoE gate of its output rows (one
                 # kernel when the slabs allow: ops.linear_add_rmsnorm route)
@@ -252,7 +272,8 @@ class TransformerLM:
         return (float(getattr(kv_caches, "k_scale", 1.0)),
                 float(getattr(kv_caches, "v_scale", 1.0)))
 
-    def _attend(self, qkv, b: DeviceBatch, kc, vc, kvs=(1.0, 1.0)) -> torch.Tensor:
+    def _attend(self, qkv, b: DeviceBatch, kc, vc, kvs=(1.0, 1.0), shared=None) -> torch.Tensor:
+        """``shared``: the step's ``ops.SharedPrefixPlan`` of its decode rows, or None."""
         cfg = self.cfg
         win = cfg.sliding_window                 # 0 = full attention
         ks, vs = kvs
@@ -264,7 +285,7 @@ class TransformerLM:
                 ops.decode_attention(qkv[:nd], kc, vc, b.block_tables[:nd],
                                      b.context_lens[:nd], b.max_context_decode, cfg.num_heads,
                                      cfg.num_kv_heads, cfg.head_dim, self.scale, out=out[:nd],
-                                     window=win, k_scale=ks, v_scale=vs)
+                                     window=win, k_scale=ks, v_scale=vs, shared=shared)
                 ops.prefill_attention_paged(qkv[nd:], b.cu_seqlens_prefill,
                                             b.max_seqlen_prefill, b.context_lens[nd:],
                                             b.block_tables[nd:], kc, vc, cfg.num_heads,
@@ -282,7 +303,7 @@ class TransformerLM:
                                          window=win)
         return ops.decode_attention(qkv, kc, vc, b.block_tables, b.context_lens, b.max_context,
                                     cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, self.scale,
-                                    window=win, k_scale=ks, v_scale=vs)
+                                    window=win, k_scale=ks, v_scale=vs, shared=shared)
 
     def _attention(self, qkv, b: DeviceBatch, kc, vc, kvs=(1.0, 1.0)) -> torch.Tensor:
         cfg = self.cfg

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 import time
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1180,13 +1180,68 @@ def decode_num_splits(B: int, hkv: int, max_context: int) -> int:
     return splits
 
 
+class SharedPrefixPlan(NamedTuple):
+    """What ``shared_prefix_plan`` found in a decode batch's block tables (int32 tensors on
+    their device): ``header`` = (tokens of the shared run P * block_size, member count),
+    ``members`` = the member rows ascending then -1, ``lo[b]`` = the run's tokens for a
+    member row and 0 for the rest: row b attends [0, lo[b]) with its group."""
+    header: torch.Tensor
+    members: torch.Tensor
+    lo: torch.Tensor
+
+
+SHARED_PLAN_MAX_B = 2048      # rows one plan launch takes (attention_decode_shared.hip)
+
+
+def shared_prefix_ok(B: int, hq: int, hkv: int, hd: int, window: int = 0,
+                     fp8: bool = False) -> bool:
+    """Whether ``decode_attention`` has the shared-prefix kernels for this case: a bf16
+    cache, head dim 128, full attention, GQA groups of <= 16 heads and a batch one plan
+    launch takes. The model builds a plan (and gives up the fused kernel) only then."""
+    return (0 < B <= SHARED_PLAN_MAX_B and not fp8 and hd == 128 and window <= 0
+            and hq % hkv == 0 and hq // hkv <= 16)
+
+
+def shared_prefix_plan(block_tables, context_lens, block_size: int) -> SharedPrefixPlan:
+    """The largest group of rows of a decode batch that start with the same KV block and the
+    run of leading blocks all of them share (``reference.shared_prefix_plan`` has the
+    definition; it is also the CPU path). One launch, device data in and out: inside a
+    captured graph every replay plans the tables it finds."""
+    if not _use_native(block_tables):
+        return SharedPrefixPlan(*R.shared_prefix_plan(block_tables, context_lens, block_size))
+    B = block_tables.shape[0]
+    if B > SHARED_PLAN_MAX_B:
+        raise ValueError(f"shared_prefix_plan: {B} rows, at most {SHARED_PLAN_MAX_B}")
+    if block_tables.dtype != torch.int32 or context_lens.dtype != torch.int32:
+        raise TypeError("shared_prefix_plan: int32 block_tables and context_lens")
+    header = torch.empty(2, dtype=torch.int32, device=block_tables.device)
+    members = torch.empty(B, dtype=torch.int32, device=block_tables.device)
+    lo = torch.empty(B, dtype=torch.int32, device=block_tables.device)
+    _native_call("dli_decode_shared_plan", _p(header), _p(members), _p(lo), _p(block_tables),
+                 block_tables.stride(0), block_tables.shape[1], _p(context_lens), B,
+                 int(block_size), _st())
+    return SharedPrefixPlan(header, members, lo)
+
+
+def shared_prefix_chunks(n: int) -> int:
+    """Force the chunk count of the shared run (1..16; 0 = automatic); returns the old value.
+    For ``scripts/attn_probe.py``'s sweep: process-wide, and not to be changed while a captured
+    graph that holds a shared-prefix attention is live."""
+    return int(N.require_native().dli_decode_shared_set_chunks(int(n)))
+
+
 def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_context: int,
                      hq, hkv, hd, scale, out=None, num_splits: Optional[int] = None,
-                     window: int = 0, k_scale: float = 1.0, v_scale: float = 1.0):
+                     window: int = 0, k_scale: float = 1.0, v_scale: float = 1.0,
+                     shared: Optional[SharedPrefixPlan] = None):
     """One query per row of ``qkv`` (rows = sequences) against its paged KV; [B, Hq*hd].
     ``window`` > 0: sliding-window attention, sequence b attends over the keys
     [max(0, context_lens[b] - window), context_lens[b]). ``k_scale`` / ``v_scale``: the
-    scales of an FP8 cache (the wave-per-item kernel of attention_decode_fp8.hip)."""
+    scales of an FP8 cache (the wave-per-item kernel of attention_decode_fp8.hip).
+    ``shared``: the ``shared_prefix_plan`` of these block tables; the blocks its member rows
+    share are then read once per tile of sequences (attention_decode_shared.hip) for a bf16
+    cache, head dim 128, full attention and GQA groups of <= 16 heads. Any other case takes
+    the path without a plan: the same maths."""
     B = qkv.shape[0]
     window = max(int(window), 0)
     fp8 = kv_cache_is_fp8(k_cache, v_cache, k_scale, v_scale, native=_use_native(qkv))
@@ -1200,6 +1255,15 @@ def decode_attention(qkv, k_cache, v_cache, block_tables, context_lens, max_cont
         return o
     if out is None:
         out = torch.empty(B, hq * hd, dtype=qkv.dtype, device=qkv.device)
+    if shared is not None and shared_prefix_ok(B, hq, hkv, hd, window, fp8):
+        ws = G.workspace(qkv.device, int(
+            N.require_native().dli_decode_attention_shared_workspace_bytes(
+                B, hq, hkv, hd, max_context)))
+        _native_call("dli_decode_attention_shared", _p(out), _p(qkv), qkv.stride(0),
+                     _p(k_cache), _p(v_cache), _p(block_tables), block_tables.stride(0),
+                     _p(context_lens), _p(shared.header), _p(shared.members), _p(shared.lo), B,
+                     hq, hkv, hd, k_cache.shape[2], scale, max_context, _p(ws), _st())
+        return out
     if num_splits is None:
         num_splits = decode_num_splits(B, hkv, decode_span(max_context, window))
     ws = None

@@ -43,6 +43,12 @@ _SIGS = {
     # the paged-cache readers: ..., window, kv_fp8, k_scale, v_scale, stream
     "dli_decode_attention": [P, P, I, P, P, P, I, P, I, I, I, I, I, F, I, I, P, I, I, F, F, P],
     "dli_decode_attention_workspace_bytes": [I, I, I, I],
+    # shared-prefix decode attention: the plan (header, members, lo <- tables, stride, width,
+    # ctx, B, block size) and the attention that takes it in place of window / FP8 arguments
+    "dli_decode_shared_plan": [P, P, P, P, I, I, P, I, I, P],
+    "dli_decode_attention_shared": [P, P, I, P, P, P, I, P, P, P, P, I, I, I, I, I, F, I, P, P],
+    "dli_decode_attention_shared_workspace_bytes": [I, I, I, I, I],
+    "dli_decode_shared_set_chunks": [I],
     "dli_prefill_attention": [P, I, P, I, P, I, I, I, I, I, F, I, P],
     "dli_prefill_set_min_len": [I],
     "dli_prefill_set_pack": [I],

@@ -463,6 +463,42 @@ def decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale,
     return out
 
 
+def shared_prefix_plan(block_tables: torch.Tensor, context_lens: torch.Tensor, block_size: int):
+    """(header, members, lo), int32 on the tables' device, of a decode batch [B, W]:
+
+    * live rows: context_lens[b] > 0. The rows that pad a captured batch to its bucket
+      (context 0, a table of zeros) take no part, whatever block id 0 is to the others;
+    * leader: the live row whose column-0 block id occurs most often in column 0 of the live
+      rows, ties to the lowest row; members: the live rows whose column 0 equals the leader's;
+    * P: the largest p such that columns 0..p-1 of every member equal the leader's and
+      p * block_size <= context_lens[b] - 1 for every member (the newest token is never in
+      the shared run; padding columns are zero and block 0 is a real block, so this bound is
+      what ends a run); fewer than 2 members: P = 0;
+    * header = (P * block_size, member count), members = the member rows ascending then -1,
+      lo[b] = P * block_size for members and 0 for the rest."""
+    dev = block_tables.device
+    bt, cl = block_tables.long(), context_lens.long()
+    B, width = bt.shape
+    live = cl > 0
+    if not bool(live.any()):
+        return (torch.zeros(2, dtype=torch.int32, device=dev),
+                torch.full((B,), -1, dtype=torch.int32, device=dev),
+                torch.zeros(B, dtype=torch.int32, device=dev))
+    col0 = bt[:, 0]
+    cnt = ((col0[:, None] == col0[None, :]) & live[None, :] & live[:, None]).sum(1)
+    leader = int((cnt == cnt.max()).nonzero()[0])
+    mem = live & (col0 == col0[leader])
+    nmem = int(mem.sum())
+    lim = min(width, int(((cl[mem] - 1) // block_size).min()))
+    same = (bt[mem, :lim] == bt[leader, :lim]).all(0)
+    P = int(same.long().cumprod(0).sum()) if nmem >= 2 else 0
+    members = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    members[:nmem] = mem.nonzero().flatten().to(torch.int32)
+    lo = torch.where(mem, P * block_size, 0).to(torch.int32)
+    header = torch.tensor([P * block_size, nmem], dtype=torch.int32, device=dev)
+    return header, members, lo
+
+
 # ----------------------------------------------------------------------------- sampling (K13)
 def topk_topp_filter(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
                      top_p: torch.Tensor) -> torch.Tensor:

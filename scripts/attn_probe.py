@@ -11,8 +11,11 @@ split count the engine would run. ``--kv-dtype bf16,fp8`` adds a row per case fo
 (e4m3fn) cache: its writer ("rope") and its one attention kernel with the engine's split count
 ("auto"; there is no fused or pipelined FP8 form), the bytes counted at one per element.
 
+``--shared-prefix P,..`` times the shared-prefix path instead (``shared_prefix_cases``).
+
     python scripts/attn_probe.py [--batch 64,512] [--ctx 1,33,66,100,200,400] [--window W]
                                  [--kv-dtype bf16,fp8]
+    python scripts/attn_probe.py --batch 64,512 --shared-prefix 0,256,1024,4096 [--suffix 64]
 """
 import argparse
 import json
@@ -24,6 +27,77 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 
+def shared_prefix_cases(a, ops, dev, hq, hkv, hd, bs):
+    """Batch x shared prefix x suffix: every row starts with the same prefix / bs blocks and
+    goes on with private blocks for ``--suffix`` tokens. "fused" is the kernel the decode
+    graph runs today, "rope" + "shared" what it runs with the shared-prefix switch on (the
+    plan is timed apart: it runs once per step, not per layer), "plain" today's unfused
+    attention. The forms alternate ``--rounds`` times and the median round is printed. Both
+    rates count the bytes of every row's whole context: what a path without sharing reads."""
+    N = (hq + 2 * hkv) * hd
+    scale = hd ** -0.5
+    prefixes = [int(p) for p in a.shared_prefix.split(",")]
+    cos_sin = torch.randn(max(prefixes) + a.suffix + 1, hd, device=dev)
+    if a.chunks:
+        ops.shared_prefix_chunks(a.chunks)
+    for B in [int(b) for b in a.batch.split(",")]:
+        for prefix in prefixes:
+            ctx = prefix + a.suffix
+            np_, ns_ = prefix // bs, -(-ctx // bs) - prefix // bs
+            nblk = np_ + B * ns_ + 8
+            kc = torch.randn(nblk, hkv, bs, hd, device=dev, dtype=torch.bfloat16) * 0.5
+            vc = torch.randn(nblk, hkv, bs, hd, device=dev, dtype=torch.bfloat16) * 0.5
+            run = torch.arange(np_, device=dev, dtype=torch.int32).expand(B, np_)
+            own = (np_ + torch.randperm(B * ns_, device=dev).to(torch.int32)).view(B, ns_)
+            bt = torch.cat([run, own], 1).contiguous()
+            cl = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+            pos = cl - 1
+            slot = (bt[:, (ctx - 1) // bs] * bs + (ctx - 1) % bs).to(torch.int32)
+            slabs = (torch.randn(2, B, N, device=dev) * 0.02).to(torch.float16)
+            qkv = (torch.randn(B, N, device=dev) * 0.5).to(torch.bfloat16)
+            out = torch.empty(B, hq * hd, dtype=torch.bfloat16, device=dev)
+            plan = ops.shared_prefix_plan(bt, cl, bs)
+            assert int(plan.header[0]) == np_ * bs and int(plan.header[1]) == (B if np_ else 1)
+
+            def fused():
+                ops._native_call("dli_decode_attention_fused", ops._p(out), ops._p(slabs), 2,
+                                 ops._p(pos), ops._p(slot), ops._p(cos_sin), ops._p(kc),
+                                 ops._p(vc), ops._p(bt), bt.stride(0), ops._p(cl), B, hq, hkv,
+                                 hd, bs, scale, 1, 0, None, None, None, 0.0, ops._st())
+
+            def plain():
+                ops.decode_attention(qkv, kc, vc, bt, cl, ctx, hq, hkv, hd, scale, out=out)
+
+            def shared():
+                ops.decode_attention(qkv, kc, vc, bt, cl, ctx, hq, hkv, hd, scale, out=out,
+                                     shared=plan)
+            forms = {"fused": fused, "plain": plain, "shared": shared,
+                     "rope": lambda: ops.rope_and_cache(qkv, pos, slot, cos_sin, kc, vc, hq,
+                                                        hkv, hd),
+                     "plan": lambda: ops.shared_prefix_plan(bt, cl, bs)}
+            plain()
+            want = out.clone()
+            shared()
+            err = (out.float() - want.float()).abs().max().item()
+            us = {k: [] for k in forms}
+            for _ in range(a.rounds):
+                for name, fn in forms.items():
+                    def rep(fn=fn):
+                        for _ in range(16):
+                            fn()
+                    us[name].append(ops.benchmark(rep, iters=a.reps, warmup=1, graph=True)
+                                    / 16 * 1e3)
+            kv_mb = B * hkv * ctx * 2 * hd * 2 / 1e6
+            row = {"batch": B, "prefix": prefix, "suffix": a.suffix, "kv_MB": round(kv_mb, 1),
+                   "chunks": a.chunks, "max_abs_diff_vs_plain": round(err, 5)}
+            for name, t in us.items():
+                row[name + "_us"] = round(sorted(t)[len(t) // 2], 2)
+            row["fused_TBps"] = round(kv_mb / row["fused_us"], 3)
+            row["shared_TBps"] = round(kv_mb / (row["shared_us"] + row["rope_us"]), 3)
+            print(json.dumps(row), flush=True)
+            del kc, vc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="512")
@@ -31,6 +105,13 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--kv-dtype", default="bf16", help="comma-separated: bf16, fp8")
+    ap.add_argument("--shared-prefix", default="", metavar="P,..",
+                    help="shared prefix lengths (multiples of 16): time the shared-prefix "
+                         "path against today's at batch x prefix x --suffix instead")
+    ap.add_argument("--suffix", type=int, default=64, help="private tokens per row")
+    ap.add_argument("--rounds", type=int, default=3, help="alternations of the forms")
+    ap.add_argument("--chunks", type=int, default=0,
+                    help="force the chunk count of the shared run (0 = automatic)")
     a = ap.parse_args()
     kv_dtypes = [d for d in a.kv_dtype.split(",") if d]
     if any(d not in ("bf16", "fp8") for d in kv_dtypes):
@@ -42,6 +123,9 @@ def main():
     R = 16
     N = (hq + 2 * hkv) * hd
     scale = hd ** -0.5
+    if a.shared_prefix:
+        shared_prefix_cases(a, ops, dev, hq, hkv, hd, bs)
+        return
     cases = [(int(b), int(c)) for b in a.batch.split(",") for c in a.ctx.split(",")]
     cos_sin = torch.randn(max(4096, max(c for _, c in cases)), hd, device=dev)
     def timed(row, forms):
